@@ -33,7 +33,23 @@ gather.  UNIPEAK_BENCH_DIST=1 takes the distributed path at N=1 too (to
 exercise RCCL on a one-GPU box).
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
-the roofline of the dominant kernel (K1a) and the oracle CPU baseline.
+the roofline of the dominant kernel (K1a) as its events in the timed steps
+give it.
+
+A plain run does what the headline needs and no more: set-up, warm-up, the
+--steps timed steps of the headline leg, the result line.  --full adds every
+measurement that takes passes of its own: the warm leg, the isolated
+per-kernel passes, the single cold passes, the HBM copy rate and the oracle
+CPU baseline (--no-cpu-baseline leaves that one out of a --full run).
+
+--dump-outputs DIR writes what the last timed step of the headline leg
+delivered to rank 0 -- the region records in global unit order, one
+DIR/<field>.npy per record field, and the per-sample counts, DIR/counts.npy --
+as float64 (every field is a 32-bit integer or a double: exact).  Every array
+is finite: where a double field holds NaN (a statistic not computed in this
+configuration, or undefined for the region) <field>.npy carries 0 and
+DIR/<field>_nonfinite.npy marks the row.  The inputs are generated from --seed, so two builds run with the same arguments can be
+compared array for array.
 """
 import argparse
 import json
@@ -124,6 +140,40 @@ def pmc_traffic(bytes_per_launch):
     return None, None
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, recs, counts, extra=None):
+    """--dump-outputs: one float64 .npy per record field, counts.npy and the
+    scalars in extra (name -> value).  Every array is finite: a double field
+    (peak_score, kurtosis, corr) may hold NaN -- a statistic the pass did not
+    compute or that is undefined for the region -- so <field>.npy carries 0
+    there and <field>_nonfinite.npy says what the record held (0 finite,
+    1 NaN, 2 +inf, 3 -inf).  Above DUMP_LIMIT_BYTES in all, the same fixed,
+    seeded sample of the rows (ascending) goes into every array."""
+    os.makedirs(path, exist_ok=True)
+    n = len(recs)
+    extra = extra or {}
+    # every array's rows, the row numbers themselves, and 256 B per file for its header and a scalar
+    doubles = [f for f in recs.dtype.names if recs.dtype[f].kind == "f"]
+    row_bytes = 8 * (len(recs.dtype.names) + len(doubles) + counts.shape[1] + 1)
+    budget = DUMP_LIMIT_BYTES - 256 * (len(recs.dtype.names) + len(doubles) + 2 + len(extra))
+    if n * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(0).choice(n, max(budget // row_bytes, 1), replace=False))
+        recs, counts = recs[rows], counts[rows]
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    for f in recs.dtype.names:
+        a = np.ascontiguousarray(recs[f]).astype(np.float64)
+        if f in doubles:
+            kind = np.where(np.isnan(a), 1.0, np.where(np.isposinf(a), 2.0, np.where(np.isneginf(a), 3.0, 0.0)))
+            np.save(os.path.join(path, f + "_nonfinite.npy"), kind)
+            a[kind != 0] = 0.0
+        np.save(os.path.join(path, f + ".npy"), a)
+    np.save(os.path.join(path, "counts.npy"), counts.astype(np.float64))
+    for k, v in extra.items():
+        np.save(os.path.join(path, k + ".npy"), np.array([v], np.float64))
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -194,8 +244,15 @@ def main():
     ap.add_argument("--workload", default="hg19-dir1", choices=sorted(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", default="all")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take passes of their own: warm leg, isolated "
+                         "per-kernel passes, single cold passes, HBM copy rate, oracle CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records and counts of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     W = WORKLOADS[args.workload]
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if W.get("shift_pipeline") and args.gpus != 1:
         raise SystemExit("hg19-shift runs on one GPU (--gpus 1)")
@@ -287,16 +344,19 @@ def main():
         g2.close()
     gen_s = time.time() - t_gen
     mine_bp = sum(lens[units[k][0]] for k in mine)
-    copy_gbps = g.hbm_copy_gbps(1 << 30, 5)
+    copy_gbps = g.hbm_copy_gbps(1 << 30, 5) if args.full else None
     # legs (DESIGN.md §3 "Index policy", §7): "cold" -- every pass reads only
     # the packed 2-bit tracks, no derived index survives between passes
     # (UP_INDEX_NEVER): the reference's one pass per run, the headline value;
     # "warm" -- the chunk-sum plane / pooled planes / pooled count tracks are
-    # built once (untimed) and reused, a parameter sweep's re-scan (value_warm)
+    # built once (untimed) and reused, a parameter sweep's re-scan (value_warm);
+    # a run without --full times the first leg only
     legs = os.environ.get("UNIPEAK_BENCH_LEGS", "cold,warm").split(",")
     policy_of = {"cold": capi.INDEX_NEVER, "warm": capi.INDEX_ALWAYS}
     if not legs or any(x not in policy_of for x in legs):
         raise SystemExit(f"UNIPEAK_BENCH_LEGS={os.environ.get('UNIPEAK_BENCH_LEGS')}: cold and/or warm")
+    if not args.full:
+        legs = legs[:1]
     g.set_index_policy(policy_of[legs[0]])
 
     phase = {"allreduce": 0.0, "launch": 0.0, "wait": 0.0, "gather_merge": 0.0}
@@ -481,7 +541,7 @@ def main():
     def run_leg(name):
         """warm-up passes, then exactly args.steps timed steps under the leg's
         index policy (barrier + sync on both sides, max over ranks), then
-        three blocking passes for the isolated per-kernel breakdown"""
+        (--full) three blocking passes for the isolated per-kernel breakdown"""
         barrier()
         g.set_index_policy(policy_of[name])
         g.set_timing(2)  # warm-up passes report every phase
@@ -523,25 +583,34 @@ def main():
         timed[0] = False
         builds = g.index_state()[1] - builds0  # index builds inside the timed steps
         dump = os.environ.get("UNIPEAK_BENCH_DUMP")
-        if final is not None and dump and name == legs[0]:  # rehearsals: the merged records of the last step
+        if args.dump_outputs and rank == 0 and final is None:
+            raise SystemExit("--dump-outputs: the records of a step reach rank 0 whole only on one node")
+        # the merged records of the last step (rehearsals: UNIPEAK_BENCH_DUMP, one .npz)
+        if final is not None and (dump or args.dump_outputs) and name == legs[0]:
             blocks, _, _ = border.blocks(final[1])
             recs = [b.copy() for _, b, _ in blocks]
             for (gunit, _, _), r in zip(blocks, recs):
                 r["unit"] = gunit  # rank-local unit id -> global unit id
-            np.savez(dump, recs=np.concatenate(recs) if recs else np.zeros(0, capi.REGION_DTYPE),
-                     counts=np.concatenate([c for _, _, c in blocks]) if blocks else np.zeros((0, S), np.uint32))
+            recs = np.concatenate(recs) if recs else np.zeros(0, capi.REGION_DTYPE)
+            counts = np.concatenate([c for _, _, c in blocks]) if blocks else np.zeros((0, S), np.uint32)
+            if dump:
+                np.savez(dump, recs=recs, counts=counts)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, recs, counts, {"n_regions": len(recs)})
         if final is not None:  # the last step's records: accepted count (outside the timing)
             final = (final[0], sum(int(np.count_nonzero(r["accepted"])) for r, _ in final[1] if len(r)))
         # after the timed region: blocking passes (nothing overlapping) for the
-        # per-kernel breakdown of one pass on an otherwise idle GPU
-        iso = []
-        if pipelined:
-            g.set_record_target(nr.my_slot_address(it[0]), cap)
-        g.set_timing(2)
-        for _ in range(3):
-            g.run()
-            iso.append(g.timings())
-        iso = [float(np.median([t[k] for t in iso])) for k in range(5)]
+        # per-kernel breakdown of one pass on an otherwise idle GPU (--full)
+        iso = None
+        if args.full:
+            iso = []
+            if pipelined:
+                g.set_record_target(nr.my_slot_address(it[0]), cap)
+            g.set_timing(2)
+            for _ in range(3):
+                g.run()
+                iso.append(g.timings())
+            iso = [float(np.median([t[k] for t in iso])) for k in range(5)]
         # K1a = K1 minus its exact part (timing level 1: K1b = 0); level-0 passes carry no events
         k1a = [t[0] - t[4] for t in done_times if t[0] > 0] or [t[0] for t in done_times]
         k1a_ms = float(np.mean(k1a))
@@ -573,13 +642,13 @@ def main():
     k1_ms = k1a_ms
     # one cold pass as a user's single run pays it (blocking up_run: first
     # launch -> records in host memory), median of 5: without the index
-    # (the headline's pass), and with the index built inside it
+    # (the headline's pass), and with the index built inside it (--full)
     single = {}
     if pipelined:
         g.set_record_target(nr.my_slot_address(it[0]), cap)
     g.set_timing(0)
     for tag, pol in ((("no_index", capi.INDEX_NEVER), ("index_built_in_pass", capi.INDEX_ALWAYS))
-                     if os.environ.get("UNIPEAK_BENCH_SINGLE", "1") != "0" else ()):
+                     if args.full and os.environ.get("UNIPEAK_BENCH_SINGLE", "1") != "0" else ()):
         g.set_index_policy(pol)
         ts = []
         for _ in range(5):
@@ -596,7 +665,7 @@ def main():
                               "legs_ms_per_step": {k: round(v["dt"] * 1e3, 4) for k, v in res_leg.items()},
                               "shard_bp": int(sum(lens[units[k][0]] * nstr for k in mine)), "k1a_ms": round(k1a_ms, 4),
                               "k1_ms": round(k1_ms, 4), "warmup_timings_ms": [round(x, 4) for x in warm],
-                              "isolated_ms": [round(x, 4) for x in iso]}), flush=True)
+                              "isolated_ms": iso and [round(x, 4) for x in iso]}), flush=True)
             g.set_record_target(0, 0)
             g.close()
             if pool is not None:
@@ -646,15 +715,17 @@ def main():
                                          if dens == 64 else f"{TB}-bit counts of every pooled track") + ")"),
                          "kernel_note": "mean K1a duration over the timed passes (HIP events on the pass "
                                         "stream); passes overlap, so K1a shares the GPU with earlier "
-                                        "passes' K1b/K2/K3",
-                         "isolated_ms": {"k1a": round(iso[0] - iso[4], 4), "k1b_k1x": round(iso[4], 4),
-                                         "k2": round(iso[1], 4), "k3": round(iso[2], 4),
-                                         "pass_wall": round(iso[3], 4)},
-                         "frac_isolated": round(alg_bytes / ((iso[0] - iso[4]) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         "hbm_copy_GBps": round(copy_gbps, 1),
-                         "frac_of_copy_rate": round(achieved / copy_gbps, 4)},
+                                        "passes' K1b/K2/K3"},
             "setup_s": round(gen_s, 2),
         }
+        if args.full:  # the figures of the passes taken beside the timed steps
+            res["roofline"].update({
+                "isolated_ms": {"k1a": round(iso[0] - iso[4], 4), "k1b_k1x": round(iso[4], 4),
+                                "k2": round(iso[1], 4), "k3": round(iso[2], 4),
+                                "pass_wall": round(iso[3], 4)},
+                "frac_isolated": round(alg_bytes / ((iso[0] - iso[4]) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                "hbm_copy_GBps": round(copy_gbps, 1),
+                "frac_of_copy_rate": round(achieved / copy_gbps, 4)})
         # SURVEY §8(d)'s pricing: one uint32 count per bp per strand per
         # non-control sample (8 * S_nc B/bp over both strands), beside the
         # layout's algorithmic bytes the kernel actually reads
@@ -685,16 +756,17 @@ def main():
                                                       "k3": round(Lg["iso"][2], 4), "pass_wall": round(Lg["iso"][3], 4)}},
                          "regions": {"candidates": int((Lg["final"] or (0, 0))[0]),
                                      "accepted": int((Lg["final"] or (0, 0))[1])}}
-        res["single_pass_ms"] = {k: {"median": round(float(np.median(v)), 4), "runs": [round(x, 4) for x in v]}
-                                 for k, v in single.items()} or None
-        res["single_pass_note"] = ("one blocking up_run on an idle GPU, first launch -> records in host memory, "
-                                   "median of 5; no_index: the headline's cold pass; index_built_in_pass: "
-                                   "up_invalidate_index, then a pass that builds the planes/pooled tracks first")
+        if args.full:
+            res["single_pass_ms"] = {k: {"median": round(float(np.median(v)), 4), "runs": [round(x, 4) for x in v]}
+                                     for k, v in single.items()} or None
+            res["single_pass_note"] = ("one blocking up_run on an idle GPU, first launch -> records in host memory, "
+                                       "median of 5; no_index: the headline's cold pass; index_built_in_pass: "
+                                       "up_invalidate_index, then a pass that builds the planes/pooled tracks first")
         res["hw_queues"] = {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"),
                             "inherited": HWQ_INHERITED, "library_streams": 5,
                             "note": "set by bench.py before HIP initialisation; library streams: context "
                                     "(high priority), K1a (high priority), three chain streams"}
-        if world == 1 and not args.no_cpu_baseline and args.workload == "hg19-dir1":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "hg19-dir1":
             res["cpu_baseline"] = cpu_baseline(contigs, args, value, bg_set[0], last[1])
         print(json.dumps(res), flush=True)
     g.set_record_target(0, 0)
@@ -759,6 +831,7 @@ def shift_pipeline(args, W):
     ph = {k: 0.0 for k in ("shift_pass", "sort_select", "shift_scan", "histogram", "regions_pass",
                            "shift_pass_up_run", "regions_pass_up_run")}
     info = {}
+    delivered = []  # the last step's regions -s records and counts
 
     def step(timed):
         t0 = time.perf_counter()
@@ -816,9 +889,10 @@ def shift_pipeline(args, W):
         t4b = time.perf_counter()
         nb = gb.run()
         t4c = time.perf_counter()
-        regs_b, _ = gb.regions_view()
+        regs_b, cnt_b = gb.regions_view()
         acc = int(np.count_nonzero(regs_b["accepted"]))
         t5 = time.perf_counter()
+        delivered[:] = [regs_b, cnt_b]  # views, valid until gb's next pass
         if timed:
             for k, v in zip(ph, (t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, tr - t0, t4c - t4b)):
                 ph[k] += v
@@ -838,6 +912,9 @@ def shift_pipeline(args, W):
         ka.append(ga.timings()[0])
         kb.append(gb.timings()[0])
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, delivered[0], delivered[1],
+                     {"n_regions": len(delivered[0]), "best_shift": info["best_shift"]})
     alg = genome * ga.scan_density() // 1024  # K1a of each pass
     k1a = float(np.mean(ka + kb))
     res = {

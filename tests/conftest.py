@@ -32,13 +32,25 @@ def orc_bin():
     return os.path.join(ROOT, "oracle", "_build", "orc")
 
 
-@pytest.fixture(scope="session")
-def gpu_lib():
+def _torch_hip_first():
     # torch's bundled HIP runtime must initialise before the system runtime
     # our library links, or torch sees no GPU (tools/mix_probe.py)
     import torch
     if torch.cuda.is_available():
         torch.cuda.init()
+
+
+@pytest.fixture(scope="session", autouse=True)
+def torch_hip_first():
+    """Before any test: a CPU test that loads the library ahead of the first
+    gpu-marked one (a run of the whole suite on a GPU box) would otherwise
+    hide the GPU from torch for the rest of the session."""
+    _torch_hip_first()
+
+
+@pytest.fixture(scope="session")
+def gpu_lib():
+    _torch_hip_first()
     from unipeak_amd import capi
     capi.load_library()  # raises loudly if the HIP library is missing
     if capi.device_count() < 1:

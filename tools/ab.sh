@@ -13,9 +13,9 @@ for spec in "$@"; do
   v=${spec%%|*}; e=${spec#*|}
   lib=$R/unipeak_amd/lib/libunipeak_hip_$v.so; [ "$v" = base ] && lib=$R/unipeak_amd/lib/libunipeak_hip.so
   o=$R/gpurun_out/ab/r${rep}_$i
-  env $e UNIPEAK_LIB=$lib timeout -k 10 200 python "$R/bench.py" $WL --no-cpu-baseline --steps 30 --warmup 3 > "$o.json" 2> "$o.err" || { tail -3 "$o.err"; exit 1; }
+  env $e UNIPEAK_LIB=$lib timeout -k 10 200 python "$R/bench.py" --full $WL --no-cpu-baseline --steps 30 --warmup 3 > "$o.json" 2> "$o.err" || { tail -3 "$o.err"; exit 1; }
   if [ -z "$NO_SIM" ]; then
-    env $e UNIPEAK_LIB=$lib UNIPEAK_SIM_WORLD=8 UNIPEAK_SIM_RANK=4 timeout -k 10 200 python "$R/bench.py" $WL --no-cpu-baseline --steps 40 --warmup 3 > "${o}_n8.json" 2>/dev/null || exit 1
+    env $e UNIPEAK_LIB=$lib UNIPEAK_SIM_WORLD=8 UNIPEAK_SIM_RANK=4 timeout -k 10 200 python "$R/bench.py" --full $WL --no-cpu-baseline --steps 40 --warmup 3 > "${o}_n8.json" 2>/dev/null || exit 1
   fi
   echo "[$spec] $(python -c "
 import json, os

@@ -19,7 +19,7 @@ for v in "$@"; do
     *) n=$(basename "$(cd "$R/$v" && pwd)"); [ "$v" = . ] && n=head ;;
   esac
   cd "$R/$v" || exit 1
-  timeout -k 10 200 python bench.py --workload $WL --steps ${STEPS:-30} --warmup 3 --no-cpu-baseline \
+  timeout -k 10 200 python bench.py --full --workload $WL --steps ${STEPS:-30} --warmup 3 --no-cpu-baseline \
     > "$F/${n}_r$rep.json" 2> "$F/${n}_r$rep.err" || { tail -3 "$F/${n}_r$rep.err"; exit 1; }
   echo "$n r$rep: $(cut -c1-120 "$F/${n}_r$rep.json")"
   python - "$F/${n}_r$rep.json" <<'EOF'
@@ -29,7 +29,7 @@ print("   ", d["ms_per_step"], "k1a", r["kernel_ms"], "iso", r.get("isolated_ms"
 EOF
   if [ "$rep" = 1 ] && [ -z "$NO_SQ" ]; then
     (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 120 rocprofv3 --pmc $SQ --output-format csv \
-      -d "$F/${n}_sq" -o p -- python3 "$R/$v/bench.py" --workload $WL --steps 3 --warmup 1 --no-cpu-baseline \
+      -d "$F/${n}_sq" -o p -- python3 "$R/$v/bench.py" --full --workload $WL --steps 3 --warmup 1 --no-cpu-baseline \
       > "$F/${n}_sq.log" 2>&1) || { tail -3 "$F/${n}_sq.log"; exit 1; }
   fi
 done

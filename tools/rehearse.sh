@@ -9,11 +9,11 @@
 R="${GRAFT_REPO_ROOT:?}"; cd "$R" || exit 1; D=gpurun_out/rehearse; mkdir -p $D
 for W in ${WS:-hg19-dir1 hg19-8s1c}; do
   ST=20; [ "$W" = hg19-dir1 ] || ST=6
-  UNIPEAK_BENCH_DUMP=$D/${W}_n1.npz timeout -k 10 300 python bench.py --workload $W --steps $ST --warmup 2 \
+  UNIPEAK_BENCH_DUMP=$D/${W}_n1.npz timeout -k 10 300 python bench.py --full --workload $W --steps $ST --warmup 2 \
     --no-cpu-baseline > $D/${W}_n1.json 2> $D/${W}_n1.err || { tail -20 $D/${W}_n1.err; exit 1; }
   for N in ${NS:-2 4 8}; do
     UNIPEAK_BENCH_DUMP=$D/${W}_n$N.npz UNIPEAK_SHARE_GPU=1 UNIPEAK_DIST_BACKEND=gloo timeout -k 10 400 \
-      python bench.py --workload $W --gpus $N --steps $ST --warmup 2 --no-cpu-baseline \
+      python bench.py --full --workload $W --gpus $N --steps $ST --warmup 2 --no-cpu-baseline \
       > $D/${W}_n$N.json 2> $D/${W}_n$N.err || { tail -20 $D/${W}_n$N.err; exit 1; }
     python - "$D/${W}_n1.npz" "$D/${W}_n$N.npz" "$D/${W}_n$N.json" "$W" "$N" <<'EOF' || exit 1
 import json, sys
