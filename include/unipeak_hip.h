@@ -180,14 +180,16 @@ int up_reset_units(up_ctx *ctx);
  * bw > UP_MAX_PARALLEL_BW (511: K1's register-resident halo of NH <= 8
  * 64-position words) on directional units with a threshold > 0 runs K1w,
  * the parallel scan for wide kernels (up to 32767, a window of 65535 cells;
- * pipelined like K1; no dense profile).  Wider kernels (32768..65535, where
+ * pipelined like K1, with or without the -w capture; its dense profile comes
+ * from wide_profile_kernel).  Wider kernels (32768..65535, where
  * the reference's UShort retirement count wraps, misc/peakcall.cpp:172-177)
- * take the whole-buffer replay.  A negative coefficient at a threshold <= 0, the -w
- * capture with a head unit or with bw > 511, and bw > 511 on nondirectional
- * units or at a threshold <= 0 run the exact state machine over every unit
- * instead (K0, as independent chains from every run start: exact, far
- * slower than the scans); up_run_async refuses those (UP_E_UNSUPPORTED),
- * up_unit_profile* refuse them and bw > 511.  up_shift_scan correlates a
+ * take the whole-buffer replay.  A negative coefficient at a threshold <= 0,
+ * the -w capture with a head unit at a threshold <= 0, and bw > 511 on
+ * nondirectional units, at a threshold <= 0 or from 32768 on run the exact
+ * state machine over every unit instead (K0, as independent chains from
+ * every run start, one chain per buffer with the -w capture on: exact, far
+ * slower than the scans); up_run_async and up_unit_profile* refuse those
+ * (UP_E_UNSUPPORTED).  up_shift_scan correlates a
  * replayed region's stored scores (Region::scores), as strandCorr does.
  * With a threshold <= 0 the last region of a unit is still open after its
  * flush and is closed in the buffer's next unit (UP_CLOSE_Q11_HEAD); the
@@ -282,18 +284,27 @@ int up_index_state(up_ctx *ctx, int *on, uint64_t *builds);
  * else 1024 * up_track_bits() / 8 per pooled track and strand */
 int up_scan_density(up_ctx *ctx, uint32_t *bytes_per_1024);
 /* device-side timings of the last up_run in ms: [0]=K1 scan, [1]=K2
- * segment, [2]=K3 stats, [3]=whole up_run wall, [4]=K1 launches */
+ * segment, [2]=K3 stats, [3]=whole up_run wall, [4]=K1 launches; with n > 5
+ * also [5]=the dense-profile kernel of the last up_unit_profile* call (HIP
+ * events around it) */
 /* achievable HBM rate: a float4 streaming copy kernel of `bytes` (a multiple
  * of 16; best of reps),
  * GB/s counting read + write (the bench's copy-rate reference) */
 int up_hbm_copy_gbps(up_ctx *ctx, uint64_t bytes, int reps, double *gbps);
 int up_timings(up_ctx *ctx, double *ms, int n);
-/* dense per-position score f+r of one unit (testing/-w): out[len] */
+/* dense per-position score f+r of one unit (testing/-w): out[len].  K1's
+ * fused profile path up to UP_MAX_PARALLEL_BW; wider kernels where K1w runs
+ * (directional units, a threshold > 0, bw up to 32767): wide_profile_kernel,
+ * every score the ascending sum K1w forms, out_r all zero.  Refused
+ * (UP_E_UNSUPPORTED) wherever up_run takes the exact replay of every unit. */
 int up_unit_profile(up_ctx *ctx, uint32_t unit, double *out_f, double *out_r,
                     uint32_t len);
 /* -w for units the exact replay produced (K0: quirk Q1 head hits, -r <= 0
  * with a unit processing position 1 or a negative coefficient,
- * bw > UP_MAX_PARALLEL_BW), whose retirements the dense KDE does not reproduce.  With the
+ * bw > UP_MAX_PARALLEL_BW outside K1w), whose retirements the dense KDE does not
+ * reproduce.  (A K1w pass keeps running K1w with the capture on: units without
+ * head hits report resync = 0 and no entries, head units the K0 head replay's
+ * entries and its resync point, as K1 passes do.)  With the
  * capture on before up_run, the replay records every processPosition() with
  * a nonzero score (misc/peakcall.cpp:80-83: profileOut_->write), and
  * up_unit_replay_profile returns them for one unit in emission order:

@@ -369,6 +369,20 @@ class Lib:
         _ck(self.L.up_unit_profile(self.ctx, unit, f.ctypes.data, r.ctypes.data, length))
         return f, r
 
+    def profile_range(self, unit, first, count):
+        """(f, r) of positions [first, first + count), first >= 1; the range may run
+        past the contig end into the scan domain (up_unit_profile_range)"""
+        f = np.zeros(count, np.float64)
+        r = np.zeros(count, np.float64)
+        _ck(self.L.up_unit_profile_range(self.ctx, unit, first, count, f.ctypes.data, r.ctypes.data))
+        return f, r
+
+    def profile_kernel_ms(self):
+        """device time of the last profile()/profile_range() kernel (up_timings [5])"""
+        t = np.zeros(6, np.float64)
+        _ck(self.L.up_timings(self.ctx, t.ctypes.data, 6))
+        return float(t[5])
+
     def set_profile_capture(self, on):
         _ck(self.L.up_set_profile_capture(self.ctx, int(bool(on))))
 

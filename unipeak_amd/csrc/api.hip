@@ -247,6 +247,7 @@ struct up_ctx {
     std::vector<uint32_t> unit_last;
     hipEvent_t ev[8] = {};
     double times[5] = {0, 0, 0, 0, 0};
+    double prof_ms = 0;  // the dense-profile kernel of the last up_unit_profile* (HIP events)
     int timing = 2;                  // up_set_timing: 0 wall only, 1 + K1a, 2 every phase
     // passes in flight (up_run_async); slot = sequence % kSlots.  Each slot
     // owns its device buffers and its stream, so a pass's streaming K1a can
@@ -1594,8 +1595,9 @@ static bool q11_whole_replay() {
 }
 
 // K1w (wide.hip) for kernels wider than K1's halo: directional units, a
-// threshold > 0, no -w capture (its retirements come from the replay), and
-// a window of at most 65,535 cells (bw <= kMaxWideBw): the reference counts
+// threshold > 0 (with the -w capture on as well: head units hand their
+// retirements over from the K0 head replay, wide_profile_kernel gives the
+// dense rest), and a window of at most 65,535 cells (bw <= kMaxWideBw): the reference counts
 // the cells add() retires in a UShort (misc/peakcall.cpp:172-177), so from
 // bw 32,768 on a gap of 2bw + 1 or more retires (gap mod 65,536) cells, the
 // rest of the window stays misaligned and a flush leaks into the buffer's
@@ -1606,8 +1608,7 @@ static bool wide_mode(const up_ctx *c) {
         const char *e = getenv("UNIPEAK_WIDE");
         return !(e && *e == '0');
     }();
-    return on && c->p.bw > kMaxBw && c->p.bw <= kMaxWideBw && kTB == 2 && c->p.region_thr > 0 && !c->p.nondir &&
-           !c->prof_capture;
+    return on && c->p.bw > kMaxBw && c->p.bw <= kMaxWideBw && kTB == 2 && c->p.region_thr > 0 && !c->p.nondir;
 }
 
 static bool replay_mode(const up_ctx *c) {
@@ -1627,7 +1628,8 @@ static int check_runnable(up_ctx *c, bool profile = false) {
     int r = check_params(c);
     if (r) return r;
     if (replay_mode(c)) return UP_E_UNSUPPORTED;
-    if (profile && c->p.bw > kMaxBw) return UP_E_UNSUPPORTED;  // (the dense profile's window is K1's)
+    // (the dense profile's window is K1's, or wide_profile_kernel's where K1w runs)
+    if (profile && c->p.bw > kMaxBw && !wide_mode(c)) return UP_E_UNSUPPORTED;
     return q11_mode(c) && !c->q11_run && !profile ? UP_E_UNSUPPORTED : UP_OK;
 }
 
@@ -3064,6 +3066,7 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
 int up_timings(up_ctx *c, double *ms, int n) {
     if (!c || !ms) return UP_E_ARG;
     for (int i = 0; i < n && i < 5; ++i) ms[i] = c->times[i];
+    if (n > 5) ms[5] = c->prof_ms;
     return UP_OK;
 }
 
@@ -3087,11 +3090,32 @@ int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t cou
     P.prof_first = (int64_t)first;
     P.prof_len = count;
     P.prof_unit = unit;
-    const uint32_t s0 = u.strip0 + (uint32_t)((first - 1) / kStrip);
-    const uint32_t s1 = u.strip0 + (uint32_t)((first + count - 2) / kStrip) + 1;
-    dispatch_scan<true, kModeFused>(c, c->stream, P, s0, s1);
+    HIPCHK(hipEventRecord(c->ev[5], c->stream));
+    if (c->p.bw > kMaxBw) {  // wide_mode (check_runnable): the planes are current (want_index)
+        static const uint32_t cap = [] {  // UNIPEAK_WIDE_PROFILE_LIST=0: the direct window walk (A/B)
+            const char *e = getenv("UNIPEAK_WIDE_PROFILE_LIST");
+            return e && *e == '0' ? 0u : (uint32_t)kProfHits;
+        }();
+        const uint64_t nstretch = ((first + count - 2) / 64 - (first - 1) / 64) / kProfWords + 1;
+        const dim3 grid((unsigned)std::min<uint64_t>(nstretch, 1u << 16));
+        const size_t lds = prof_lds_bytes(c->p.bw);
+        const int pm = pool_mode(c);
+        if (pm == 0) hipLaunchKernelGGL(wide_profile_kernel<0>, grid, dim3(64), lds, c->stream, P, cap);
+        else if (pm == 1) hipLaunchKernelGGL(wide_profile_kernel<1>, grid, dim3(64), lds, c->stream, P, cap);
+        else hipLaunchKernelGGL(wide_profile_kernel<2>, grid, dim3(64), lds, c->stream, P, cap);
+    } else {
+        const uint32_t s0 = u.strip0 + (uint32_t)((first - 1) / kStrip);
+        const uint32_t s1 = u.strip0 + (uint32_t)((first + count - 2) / kStrip) + 1;
+        dispatch_scan<true, kModeFused>(c, c->stream, P, s0, s1);
+    }
     HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev[6], c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[6]);
+        c->prof_ms = ms;
+    }
     HIPCHK(hipMemcpy(out_f, d, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
     if (out_r) HIPCHK(hipMemcpy(out_r, d + count, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
     (void)hipFree(d);
