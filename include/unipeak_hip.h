@@ -277,6 +277,14 @@ int up_shift_best(up_ctx *ctx, const uint64_t *region_idx, size_t n,
 int up_set_index_policy(up_ctx *ctx, int policy);
 int up_invalidate_index(up_ctx *ctx);
 int up_index_state(up_ctx *ctx, int *on, uint64_t *builds);
+/* which statistics kernel (K3) the pass completed last (up_run, up_run_wait)
+ * was launched with: 0 the general kernel, 1 the batched kernel for one
+ * directional sample with a wave per region, 2 the same with a lane per
+ * region (picked when the pass before it produced >= 16,384 regions;
+ * DESIGN.md §4 "Round 6"); -1 when that pass launched no K3 (no units, the
+ * K0 replay) or no pass has completed.  For tests and A/B runs: the records
+ * do not depend on it. */
+int up_last_stats_kind(up_ctx *ctx);
 /* bytes the streaming scan (K1a) reads per 1,024 positions of a unit in the
  * index state of the moment (its algorithmic bytes): 64 when
  * it streams a chunk-sum plane (index on and bw <= 255: the pooled track's

@@ -292,6 +292,7 @@ struct up_ctx {
         uint64_t cap = 0;            // reg_cap at launch
         uint32_t ovf_cap = 0;
         int tl = 0;                  // timing level at launch
+        int k3_kind = -1;            // the K3 dispatch_stats picks for this pass (up_last_stats_kind)
         std::chrono::steady_clock::time_point t0;
         hipEvent_t ev[5] = {};       // K1a begin, K1a end, K1b end, K2 end, K3 end
         hipEvent_t done = nullptr;
@@ -387,6 +388,7 @@ struct up_ctx {
     void *target_host = nullptr;  // host buffer we registered for it
     std::vector<void *> host_regs; // up_host_register ranges (unregistered at close)
     uint64_t last_nreg = 0;
+    int last_k3_kind = -1;  // K3 of the pass completed last (up_last_stats_kind)
 };
 
 static bool busy(const up_ctx *c) { return c && c->seq_launched != c->seq_done; }
@@ -458,6 +460,8 @@ int up_index_state(up_ctx *c, int *on, uint64_t *builds) {
     if (builds) *builds = c->index_builds;
     return UP_OK;
 }
+
+int up_last_stats_kind(up_ctx *c) { return c ? c->last_k3_kind : -1; }
 
 const char *up_strerror(int code) {
     switch (code) {
@@ -1528,7 +1532,9 @@ static StatParams stat_params(up_ctx *c, up_ctx::Pass &ps) {
     return P;
 }
 
-static void dispatch_stats(up_ctx *c, hipStream_t st, const StatParams &P, uint64_t nreg) {
+// which K3 a pass with the region estimate `nreg` runs: 0 the general kernel,
+// 1 stats1_kernel (a wave per region), 2 stats1L_kernel (a lane per region)
+static int k3_kind_for(const up_ctx *c, const StatParams &P, uint64_t nreg) {
     // one pooled directional sample with K1b's peaks: the batched K3
     // (stats1.hip; UNIPEAK_K3_ONE=0 keeps the general kernel, for A/B and tests)
     const bool one = c->k3_one && kTB == 2 && pool_mode(c) == 0 && c->p.nondir == 0 && c->p.n_samples == 1 &&
@@ -1549,7 +1555,13 @@ static void dispatch_stats(up_ctx *c, hipStream_t st, const StatParams &P, uint6
     // profiles/r06/ab_k3.txt) -- the pass's estimate of its region count
     // (the last pass's) picks
     constexpr uint64_t kK3LaneMin = 16384;
-    const int kind = one ? ((lane_k3 == 2 || (lane_k3 == 1 && nreg >= kK3LaneMin)) ? 2 : 1) : 0;
+    return one ? ((lane_k3 == 2 || (lane_k3 == 1 && nreg >= kK3LaneMin)) ? 2 : 1) : 0;
+}
+
+// (launch_pass records k3_kind_for of the same arguments for up_last_stats_kind:
+// a pass that replays a cached graph does not come through here)
+static void dispatch_stats(up_ctx *c, hipStream_t st, const StatParams &P, uint64_t nreg) {
+    const int kind = k3_kind_for(c, P, nreg);
     // (beyond 256 samples one LDS row of exptSums per wave, kernels.hip add_es)
     const size_t lds = kind == 2 ? kStat1LLds : kind == 1 ? kStat1Lds
                                                           : kStatLds + (c->p.n_samples > 256 ? 4 * 4 * (size_t)c->p.n_samples : 0);
@@ -2264,6 +2276,7 @@ static int launch_pass(up_ctx *c, int slot) {
     HIPCHK(hipEventRecord(k1a_end, s1));
     HIPCHK(hipStreamWaitEvent(ps.stream, k1a_end, 0));
     const uint32_t kw = c->k1a_waves, kx = c->k1a_xcap;
+    ps.k3_kind = k3_kind_for(c, P, std::max<uint64_t>(ps.req_last_nreg, 1024));  // (dispatch_stats' arguments)
     if (!graph || tl >= 2) {
         if (int r = enqueue_rest(c, slot, SP, P, cap, kw, kx, tl >= 2)) return r;
         HIPCHK(hipEventRecord(ps.done, ps.stream));
@@ -2416,6 +2429,7 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     c->host_regions = false;
     c->q11_placed = false;
     c->cur_slot = slot;
+    c->last_k3_kind = -1;
     if (c->units.empty()) {
         ++c->seq_done;
         if (n_regions) *n_regions = 0;
@@ -2476,6 +2490,7 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     }
     c->nreg = nreg;
     c->last_nreg = nreg;
+    c->last_k3_kind = ps.k3_kind;
     // (a K1q pass's head units take q11_finish's chains instead)
     int r = ps.req_q11 ? UP_OK : replay_head_hits(c, slot);
     if (r) return fail(r);
@@ -2592,6 +2607,7 @@ static int run_replay(up_ctx *c, uint64_t *n_regions) {
     c->nreg = 0;
     c->host_regions = false;
     c->q11_placed = false;
+    c->last_k3_kind = -1;  // K0 computes the replay's statistics
     c->h_regions.clear();
     c->h_counts.clear();
     c->h_emulated.clear();
