@@ -285,6 +285,14 @@ int up_index_state(up_ctx *ctx, int *on, uint64_t *builds);
  * K0 replay) or no pass has completed.  For tests and A/B runs: the records
  * do not depend on it. */
 int up_last_stats_kind(up_ctx *ctx);
+/* which exact kernel (K1b) the pass completed last was launched with: 0 the
+ * generic scan kernel's exact mode, 1 the pipelined kernel for one pooled
+ * directional sample with the Q keys on (DESIGN.md §4 "K1b for one
+ * directional sample"; UNIPEAK_K1B_ONE=0 at up_open keeps the generic one);
+ * -1 when that pass launched no K1b (no units, a threshold <= 0, a bandwidth
+ * above 511, the K0 replay) or no pass has completed.  For tests and A/B
+ * runs: the records do not depend on it. */
+int up_last_exact_kind(up_ctx *ctx);
 /* bytes the streaming scan (K1a) reads per 1,024 positions of a unit in the
  * index state of the moment (its algorithmic bytes): 64 when
  * it streams a chunk-sum plane (index on and bw <= 255: the pooled track's

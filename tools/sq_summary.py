@@ -10,6 +10,7 @@ import re
 import sys
 
 KERNELS = [("K1a", r"scan_kernel<1, 0, false, false, 1>"), ("K1b", r"scan_kernel<1, 0, false, false, 2>"),
+           ("K1b", r"exact1_kernel<1>"),  # (the same family: one directional sample, exact1.hip)
            ("K3", r"stats_kernel<1, 0, false>")]
 
 

@@ -7,7 +7,7 @@ import glob
 import re
 import sys
 
-NAMES = [("scan_kernel<.*, 1>", "K1a"), ("xref_kernel", "K1x"), ("scan_kernel<.*, 2>", "K1b"),
+NAMES = [("scan_kernel<.*, 1>", "K1a"), ("xref_kernel", "K1x"), ("scan_kernel<.*, 2>|exact1_kernel", "K1b"),
          ("seg_count_head", "K2a"), ("seg_compact", "K2b"), ("stats_kernel", "K3")]
 
 

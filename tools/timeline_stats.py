@@ -30,6 +30,8 @@ def main():
     def short(n):
         if "k1a_fields_kernel" in n:
             return "K1a"
+        if "exact1_kernel" in n:
+            return "K1b"
         if "scan_kernel" in n:
             m = n.split(">")[0]
             return "K1a" if (m.endswith(", 1") or m.endswith(", 3")) else ("K1b" if m.endswith(", 2") else "K1?")

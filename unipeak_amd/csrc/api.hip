@@ -21,6 +21,7 @@
 
 #include "kernels.hip"  // device code shared with the per-NH units (nh_tu.hip)
 #include "stats1.hip"   // (its LDS size)
+#include "exact1.hip"   // (its LDS size)
 #include "emulate.hip"
 #include "q11place.hip"
 #include "wide.hip"
@@ -36,6 +37,14 @@ const void *scan_kernel_nh5(int, bool, bool, int);
 const void *scan_kernel_nh6(int, bool, bool, int);
 const void *scan_kernel_nh7(int, bool, bool, int);
 const void *scan_kernel_nh8(int, bool, bool, int);
+const void *exact1_kernel_nh1();
+const void *exact1_kernel_nh2();
+const void *exact1_kernel_nh3();
+const void *exact1_kernel_nh4();
+const void *exact1_kernel_nh5();
+const void *exact1_kernel_nh6();
+const void *exact1_kernel_nh7();
+const void *exact1_kernel_nh8();
 const void *stats_kernel_nh1(int, bool, int);
 const void *stats_kernel_nh2(int, bool, int);
 const void *stats_kernel_nh3(int, bool, int);
@@ -54,6 +63,18 @@ const void *shift_kernel_nh7(int);
 const void *shift_kernel_nh8(int);
 // window words on each side of an output word: ceil((bw + 1) / 64)
 static int window_nh(int bw) { return (bw + 64) / 64; }
+static const void *exact1_kernel_for(int bw) {
+    switch (window_nh(bw)) {
+    case 1: return exact1_kernel_nh1();
+    case 2: return exact1_kernel_nh2();
+    case 3: return exact1_kernel_nh3();
+    case 4: return exact1_kernel_nh4();
+    case 5: return exact1_kernel_nh5();
+    case 6: return exact1_kernel_nh6();
+    case 7: return exact1_kernel_nh7();
+    default: return exact1_kernel_nh8();
+    }
+}
 static const void *scan_kernel_for(int bw, int pool, bool nd, bool prof, int mode) {
     switch (window_nh(bw)) {
     case 1: return scan_kernel_nh1(pool, nd, prof, mode);
@@ -183,6 +204,8 @@ struct up_ctx {
     int k1a_per_cu = 3;
     int k1b_per_cu = 0;              // K1b workgroups per CU (UNIPEAK_K1B_PER_CU; 0 = resident)
     int k3_per_cu = 0;               // K3 workgroups per CU (UNIPEAK_K3_PER_CU; 0 = resident)
+    int k1b_blocks = 0;              // K1b grid of exactly this many workgroups (UNIPEAK_K1B_BLOCKS; tests, A/B)
+    bool k1b_one = true;             // pipelined K1b for one directional sample (UNIPEAK_K1B_ONE=0: off)
     bool k3_one = true;              // batched K3 for one directional sample (UNIPEAK_K3_ONE=0: off)
     bool use_graphs = true;          // passes as hipGraphs (UNIPEAK_GRAPHS=0: plain launches)
     // streams of the passes: every K1a on one high-priority stream (stream
@@ -292,6 +315,7 @@ struct up_ctx {
         uint64_t cap = 0;            // reg_cap at launch
         uint32_t ovf_cap = 0;
         int tl = 0;                  // timing level at launch
+        int k1b_kind = -1;           // the K1b this pass launches (up_last_exact_kind)
         int k3_kind = -1;            // the K3 dispatch_stats picks for this pass (up_last_stats_kind)
         std::chrono::steady_clock::time_point t0;
         hipEvent_t ev[5] = {};       // K1a begin, K1a end, K1b end, K2 end, K3 end
@@ -388,6 +412,7 @@ struct up_ctx {
     void *target_host = nullptr;  // host buffer we registered for it
     std::vector<void *> host_regs; // up_host_register ranges (unregistered at close)
     uint64_t last_nreg = 0;
+    int last_k1b_kind = -1;  // K1b of the pass completed last (up_last_exact_kind)
     int last_k3_kind = -1;  // K3 of the pass completed last (up_last_stats_kind)
 };
 
@@ -462,6 +487,7 @@ int up_index_state(up_ctx *c, int *on, uint64_t *builds) {
 }
 
 int up_last_stats_kind(up_ctx *c) { return c ? c->last_k3_kind : -1; }
+int up_last_exact_kind(up_ctx *c) { return c ? c->last_k1b_kind : -1; }
 
 const char *up_strerror(int code) {
     switch (code) {
@@ -515,6 +541,8 @@ int up_open(int hip_device, up_ctx **out) {
     if (const char *e = getenv("UNIPEAK_K1B_PER_CU")) c->k1b_per_cu = atoi(e);
     if (const char *e = getenv("UNIPEAK_K3_PER_CU")) c->k3_per_cu = atoi(e);
     if (const char *e = getenv("UNIPEAK_K3_ONE")) c->k3_one = atoi(e) != 0;
+    if (const char *e = getenv("UNIPEAK_K1B_ONE")) c->k1b_one = atoi(e) != 0;
+    if (const char *e = getenv("UNIPEAK_K1B_BLOCKS")) c->k1b_blocks = std::max(0, atoi(e));
     if (const char *e = getenv("UNIPEAK_CHAINS")) c->n_chain = std::min(4, std::max(1, atoi(e)));
     if (const char *e = getenv("UNIPEAK_LAUNCHER")) c->use_launcher = e[0] != '0';
     {
@@ -1466,6 +1494,7 @@ static void dispatch_scan(up_ctx *c, hipStream_t st, const ScanParams &P, uint32
         // resident grid is as fast there and 2.8 % faster at N=1 (hg19, four
         // alternating pairs: 4,332 vs 4,214 Gbp/s, UNIPEAK_K1B_PER_CU A/B)
         if (c->k1b_per_cu > 0) blocks = (uint32_t)c->k1b_per_cu * (uint32_t)(c->ncu > 0 ? c->ncu : 256);
+        if (c->k1b_blocks > 0) blocks = (uint32_t)c->k1b_blocks;
     } else {
         if (kScr) {
             // K1a leaves room on every CU for the previous pass's K1b/K3
@@ -1484,6 +1513,28 @@ static void dispatch_scan(up_ctx *c, hipStream_t st, const ScanParams &P, uint32
         c->k1a_xcap = Q.xcap = (e - b + c->k1a_waves - 1) / c->k1a_waves;
     }
     void *args[] = {&Q, &b, &e};
+    (void)hipLaunchKernel(k, dim3(blocks), dim3(256), args, lds, st);
+}
+
+// which K1b a pass runs: 1 exact1_kernel (one pooled directional sample with
+// the Q keys on: exact1.hip; UNIPEAK_K1B_ONE=0 keeps the generic kernel, for
+// A/B and tests), 0 scan_kernel's exact mode
+static int k1b_kind_for(const up_ctx *c) {
+    return c->k1b_one && kTB == 2 && pool_mode(c) == 0 && c->p.nondir == 0 && c->p.bw <= kMaxBw && q_mode(c) ? 1 : 0;
+}
+
+static void dispatch_exact(up_ctx *c, hipStream_t st, const ScanParams &P, uint32_t ns) {
+    if (k1b_kind_for(c) == 0) {
+        dispatch_scan<false, kModeExact>(c, st, P, 0, ns);
+        return;
+    }
+    const void *k = exact1_kernel_for(P.bw);
+    const size_t lds = exact1_lds(P.bw, window_nh(P.bw));
+    uint32_t blocks = resident_blocks(c, k, lds);  // (the grid: see dispatch_scan)
+    if (c->k1b_per_cu > 0) blocks = (uint32_t)c->k1b_per_cu * (uint32_t)(c->ncu > 0 ? c->ncu : 256);
+    if (c->k1b_blocks > 0) blocks = (uint32_t)c->k1b_blocks;
+    ScanParams Q = P;
+    void *args[] = {&Q};
     (void)hipLaunchKernel(k, dim3(blocks), dim3(256), args, lds, st);
 }
 
@@ -2110,7 +2161,7 @@ static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatPar
                                k1a_xcap, ps.d_xref.p, ps.d_xcount.p);
             HIPCHK(hipGetLastError());
         }
-        dispatch_scan<false, kModeExact>(c, ps.stream, SP, 0, ns);    // K1b: exact blocks
+        dispatch_exact(c, ps.stream, SP, ns);    // K1b: exact blocks
         HIPCHK(hipGetLastError());
     }
     if (events) HIPCHK(hipEventRecord(ps.ev[2], ps.stream));
@@ -2277,6 +2328,8 @@ static int launch_pass(up_ctx *c, int slot) {
     HIPCHK(hipStreamWaitEvent(ps.stream, k1a_end, 0));
     const uint32_t kw = c->k1a_waves, kx = c->k1a_xcap;
     ps.k3_kind = k3_kind_for(c, P, std::max<uint64_t>(ps.req_last_nreg, 1024));  // (dispatch_stats' arguments)
+    const int k1b_kind = (ps.req_q11 || c->p.bw > kMaxBw) ? -1 : k1b_kind_for(c);  // (enqueue_rest's K1b)
+    ps.k1b_kind = k1b_kind;
     if (!graph || tl >= 2) {
         if (int r = enqueue_rest(c, slot, SP, P, cap, kw, kx, tl >= 2)) return r;
         HIPCHK(hipEventRecord(ps.done, ps.stream));
@@ -2288,6 +2341,9 @@ static int launch_pass(up_ctx *c, int slot) {
     key_add(key, P);
     key_add(key, kw);
     key_add(key, kx);
+    key_add(key, k1b_kind);  // (the captured graph holds one K1b kernel and its grid)
+    key_add(key, c->k1b_per_cu);
+    key_add(key, c->k1b_blocks);
     key_add(key, std::max<uint64_t>(ps.req_last_nreg, 1024));
     key_add(key, (uint32_t)c->units.size());
     key_add(key, ovf_cap);
@@ -2430,6 +2486,7 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     c->q11_placed = false;
     c->cur_slot = slot;
     c->last_k3_kind = -1;
+    c->last_k1b_kind = -1;
     if (c->units.empty()) {
         ++c->seq_done;
         if (n_regions) *n_regions = 0;
@@ -2491,6 +2548,7 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     c->nreg = nreg;
     c->last_nreg = nreg;
     c->last_k3_kind = ps.k3_kind;
+    c->last_k1b_kind = ps.k1b_kind;
     // (a K1q pass's head units take q11_finish's chains instead)
     int r = ps.req_q11 ? UP_OK : replay_head_hits(c, slot);
     if (r) return fail(r);
@@ -2608,6 +2666,7 @@ static int run_replay(up_ctx *c, uint64_t *n_regions) {
     c->host_regions = false;
     c->q11_placed = false;
     c->last_k3_kind = -1;  // K0 computes the replay's statistics
+    c->last_k1b_kind = -1;
     c->h_regions.clear();
     c->h_counts.clear();
     c->h_emulated.clear();

@@ -5,6 +5,7 @@
 // launches them with hipLaunchKernel (kernels.hip holds the code).
 #include "kernels.hip"
 #include "stats1.hip"
+#include "exact1.hip"
 
 #ifndef UPK_NH_TU
 #error "compile with -DUPK_NH_TU=1..8"
@@ -43,6 +44,9 @@ const void *UPK_CAT(scan_kernel_nh, UPK_NH_TU)(int pool, bool nd, bool prof, int
     if (pool == 1) return scan_ptr<1, false>(prof, mode);
     return scan_ptr<2, false>(prof, mode);
 }
+
+// K1b for one pooled directional sample with the Q keys on (exact1.hip)
+const void *UPK_CAT(exact1_kernel_nh, UPK_NH_TU)() { return (const void *)exact1_kernel<kNH>; }
 
 // K3 (one: one pooled directional sample with K1b's peaks, stats1.hip --
 // 1: a wave per region, 2: a lane per region)
