@@ -178,14 +178,22 @@ int up_reset_units(up_ctx *ctx);
  * previous unit's last run to the first clean leap past it; those records
  * name their closing add in close_pos like the whole-buffer replay's.
  * bw > UP_MAX_PARALLEL_BW (511: K1's register-resident halo of NH <= 8
- * 64-position words) on directional units with a threshold > 0 runs K1w,
- * the parallel scan for wide kernels (up to 32767, a window of 65535 cells;
- * pipelined like K1, with or without the -w capture; its dense profile comes
- * from wide_profile_kernel).  Wider kernels (32768..65535, where
+ * 64-position words) with a threshold > 0 runs K1w, the parallel scan for
+ * wide kernels (up to 32767, a window of 65535 cells).  On directional units
+ * it is pipelined like K1, with or without the -w capture, and its dense
+ * profile comes from wide_profile_kernel.  On nondirectional units it scores
+ * both strands (forwardScore + reverseScore), the strand correlation comes
+ * from wide_corr_kernel between K2 and K3 and up_shift_scan / up_shift_best
+ * form the regions' dense scores with the same sums; those passes run inside
+ * this blocking call only -- up_run_async and up_unit_profile* still refuse
+ * such a context (UP_E_UNSUPPORTED), and with the -w capture on, or under
+ * UNIPEAK_WIDE_ND=0 (read at up_open, for A/B runs), it takes the replay
+ * below.  Wider kernels (32768..65535, where
  * the reference's UShort retirement count wraps, misc/peakcall.cpp:172-177)
  * take the whole-buffer replay.  A negative coefficient at a threshold <= 0,
- * the -w capture with a head unit at a threshold <= 0, and bw > 511 on
- * nondirectional units, at a threshold <= 0 or from 32768 on run the exact
+ * the -w capture with a head unit at a threshold <= 0, and bw > 511 at a
+ * threshold <= 0, from 32768 on or on nondirectional units with the -w
+ * capture on run the exact
  * state machine over every unit instead (K0, as independent chains from
  * every run start, one chain per buffer with the -w capture on: exact, far
  * slower than the scans); up_run_async and up_unit_profile* refuse those
@@ -293,6 +301,12 @@ int up_last_stats_kind(up_ctx *ctx);
  * above 511, the K0 replay) or no pass has completed.  For tests and A/B
  * runs: the records do not depend on it. */
 int up_last_exact_kind(up_ctx *ctx);
+/* how the pass completed last found its regions: 0 K1 (K1a + K1b), 1 K1w
+ * (bw above 511), 2 K1q (a threshold <= 0), 3 the exact replay of every unit
+ * (K0); -1 when no pass has completed or it had no units.  The K0 chains of
+ * head units inside a K1 / K1w / K1q pass do not change the value.  For
+ * tests and A/B runs: the records do not depend on it. */
+int up_last_scan_kind(up_ctx *ctx);
 /* bytes the streaming scan (K1a) reads per 1,024 positions of a unit in the
  * index state of the moment (its algorithmic bytes): 64 when
  * it streams a chunk-sum plane (index on and bw <= 255: the pooled track's
@@ -300,7 +314,8 @@ int up_last_exact_kind(up_ctx *ctx);
  * else 1024 * up_track_bits() / 8 per pooled track and strand */
 int up_scan_density(up_ctx *ctx, uint32_t *bytes_per_1024);
 /* device-side timings of the last up_run in ms: [0]=K1 scan, [1]=K2
- * segment, [2]=K3 stats, [3]=whole up_run wall, [4]=K1 launches; with n > 5
+ * segment, [2]=K3 stats (with wide_corr_kernel, the strand correlation of a
+ * nondirectional K1w pass, which runs just before K3), [3]=whole up_run wall, [4]=K1 launches; with n > 5
  * also [5]=the dense-profile kernel of the last up_unit_profile* call (HIP
  * events around it) */
 /* achievable HBM rate: a float4 streaming copy kernel of `bytes` (a multiple
@@ -312,7 +327,9 @@ int up_timings(up_ctx *ctx, double *ms, int n);
  * fused profile path up to UP_MAX_PARALLEL_BW; wider kernels where K1w runs
  * (directional units, a threshold > 0, bw up to 32767): wide_profile_kernel,
  * every score the ascending sum K1w forms, out_r all zero.  Refused
- * (UP_E_UNSUPPORTED) wherever up_run takes the exact replay of every unit. */
+ * (UP_E_UNSUPPORTED) wherever up_run takes the exact replay of every unit,
+ * and for nondirectional units above UP_MAX_PARALLEL_BW (K1w finds their
+ * regions, but their dense profile is not built yet). */
 int up_unit_profile(up_ctx *ctx, uint32_t unit, double *out_f, double *out_r,
                     uint32_t len);
 /* -w for units the exact replay produced (K0: quirk Q1 head hits, -r <= 0

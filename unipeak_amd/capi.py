@@ -73,6 +73,7 @@ EXPORTS = [
     "up_host_register", "up_unit_profile_range", "up_run_async", "up_run_wait", "up_set_timing",
     "up_set_profile_capture", "up_unit_replay_profile",
     "up_set_index_policy", "up_invalidate_index", "up_index_state", "up_last_stats_kind", "up_last_exact_kind",
+    "up_last_scan_kind",
     "up_tir_open", "up_tir_close", "up_tir_set_stream", "up_tir_query", "up_tir_timings",
     "up_cm_open", "up_cm_close", "up_cm_add", "up_cm_collect", "up_cm_timings",
 ]
@@ -130,6 +131,7 @@ def load_library(path=LIB_PATH):
         "up_index_state": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_uint64)]),
         "up_last_stats_kind": (c.c_int, [vp]),
         "up_last_exact_kind": (c.c_int, [vp]),
+        "up_last_scan_kind": (c.c_int, [vp]),
         "up_unit_profile": (c.c_int, [vp, c.c_uint32, vp, vp, c.c_uint32]),
         "up_hbm_copy_gbps": (c.c_int, [vp, c.c_uint64, c.c_int, c.POINTER(c.c_double)]),
         "up_set_record_target": (c.c_int, [vp, vp, c.c_uint64]),
@@ -364,6 +366,11 @@ class Lib:
         pipelined kernel for one directional sample, -1 none launched
         (up_last_exact_kind)"""
         return int(self.L.up_last_exact_kind(self.ctx))
+
+    def last_scan_kind(self):
+        """how the pass completed last found its regions: 0 K1, 1 K1w, 2 K1q, 3 the
+        exact replay of every unit, -1 no pass or no units (up_last_scan_kind)"""
+        return int(self.L.up_last_scan_kind(self.ctx))
 
     def scan_density(self):
         """bytes K1a streams per 1,024 positions of a unit (up_scan_density)"""

@@ -207,6 +207,7 @@ struct up_ctx {
     int k1b_blocks = 0;              // K1b grid of exactly this many workgroups (UNIPEAK_K1B_BLOCKS; tests, A/B)
     bool k1b_one = true;             // pipelined K1b for one directional sample (UNIPEAK_K1B_ONE=0: off)
     bool k3_one = true;              // batched K3 for one directional sample (UNIPEAK_K3_ONE=0: off)
+    bool wide_nd = true;             // K1w for nondirectional units (UNIPEAK_WIDE_ND=0: the replay)
     bool use_graphs = true;          // passes as hipGraphs (UNIPEAK_GRAPHS=0: plain launches)
     // streams of the passes: every K1a on one high-priority stream (stream
     // order serialises them; as resources free up the dispatcher serves it
@@ -291,11 +292,13 @@ struct up_ctx {
         DevBuf<double> d_peak_val;
         DevBuf<uint64_t> d_spk;          // K1 per-strip partial peaks (ScanParams::spk)
         DevBuf<double> d_corr;           // K3 (f, r) slabs for the strand correlation (-D -y)
+        DevBuf<double> d_wcorr, d_wslab; // wide_corr_kernel: strandCorr(0) per region, its per-wave slabs
         void release() {
             d_info.release(); d_rec.release(); d_ovf_count.release(); d_ovf_rec.release(); d_head.release();
             d_cnt.release(); d_nreg.release(); d_bsum.release(); d_starts.release(); d_ends.release();
             d_runit.release(); d_peak_pos.release(); d_xlist.release(); d_xcount.release();
             d_xwcount.release(); d_xref.release(); d_peak_val.release(); d_spk.release(); d_corr.release();
+            d_wcorr.release(); d_wslab.release();
         }
         uint8_t *target = nullptr;   // record target of this pass (device address) or null
         void *target_hostp = nullptr;// host address of a host target
@@ -317,6 +320,7 @@ struct up_ctx {
         int tl = 0;                  // timing level at launch
         int k1b_kind = -1;           // the K1b this pass launches (up_last_exact_kind)
         int k3_kind = -1;            // the K3 dispatch_stats picks for this pass (up_last_stats_kind)
+        int scan_kind = -1;          // the scan this pass launches: 0 K1, 1 K1w, 2 K1q (up_last_scan_kind)
         std::chrono::steady_clock::time_point t0;
         hipEvent_t ev[5] = {};       // K1a begin, K1a end, K1b end, K2 end, K3 end
         hipEvent_t done = nullptr;
@@ -374,6 +378,7 @@ struct up_ctx {
     // and per host record the unit whose tracks hold its positions (a region
     // closed in the buffer's next unit keeps the previous unit's positions)
     bool q11_run = false;
+    bool wide_nd_run = false;  // the blocking pass of a nondirectional K1w context in progress (run_wide_nd)
     DevBuf<uint32_t> d_q11_head;
     // K1q records finished on the device (q11place.hip): K3's stage, the
     // per-unit placement, the head chains' edits, and per placed record its
@@ -414,6 +419,7 @@ struct up_ctx {
     uint64_t last_nreg = 0;
     int last_k1b_kind = -1;  // K1b of the pass completed last (up_last_exact_kind)
     int last_k3_kind = -1;  // K3 of the pass completed last (up_last_stats_kind)
+    int last_scan_kind = -1;  // how the pass completed last found its regions (up_last_scan_kind)
 };
 
 static bool busy(const up_ctx *c) { return c && c->seq_launched != c->seq_done; }
@@ -488,6 +494,7 @@ int up_index_state(up_ctx *c, int *on, uint64_t *builds) {
 
 int up_last_stats_kind(up_ctx *c) { return c ? c->last_k3_kind : -1; }
 int up_last_exact_kind(up_ctx *c) { return c ? c->last_k1b_kind : -1; }
+int up_last_scan_kind(up_ctx *c) { return c ? c->last_scan_kind : -1; }
 
 const char *up_strerror(int code) {
     switch (code) {
@@ -542,6 +549,7 @@ int up_open(int hip_device, up_ctx **out) {
     if (const char *e = getenv("UNIPEAK_K3_PER_CU")) c->k3_per_cu = atoi(e);
     if (const char *e = getenv("UNIPEAK_K3_ONE")) c->k3_one = atoi(e) != 0;
     if (const char *e = getenv("UNIPEAK_K1B_ONE")) c->k1b_one = atoi(e) != 0;
+    if (const char *e = getenv("UNIPEAK_WIDE_ND")) c->wide_nd = atoi(e) != 0;
     if (const char *e = getenv("UNIPEAK_K1B_BLOCKS")) c->k1b_blocks = std::max(0, atoi(e));
     if (const char *e = getenv("UNIPEAK_CHAINS")) c->n_chain = std::min(4, std::max(1, atoi(e)));
     if (const char *e = getenv("UNIPEAK_LAUNCHER")) c->use_launcher = e[0] != '0';
@@ -1538,6 +1546,20 @@ static void dispatch_exact(up_ctx *c, hipStream_t st, const ScanParams &P, uint3
     (void)hipLaunchKernel(k, dim3(blocks), dim3(256), args, lds, st);
 }
 
+// wide_corr_kernel's grid (one wave per workgroup, one global slab each):
+// four waves per CU
+static unsigned wide_corr_blocks(const up_ctx *c) { return 4u * (unsigned)(c->ncu > 0 ? c->ncu : 256); }
+
+// the LDS hit lists of the dense wide scores; UNIPEAK_WIDE_PROFILE_LIST=0:
+// the direct window walk (A/B)
+static uint32_t wide_list_cap() {
+    static const uint32_t cap = [] {
+        const char *e = getenv("UNIPEAK_WIDE_PROFILE_LIST");
+        return e && *e == '0' ? 0u : (uint32_t)kProfHits;
+    }();
+    return cap;
+}
+
 static StatParams stat_params(up_ctx *c, up_ctx::Pass &ps) {
     StatParams P{};
     P.units = c->d_units.p;
@@ -1657,22 +1679,31 @@ static bool q11_whole_replay() {
     return on;
 }
 
-// K1w (wide.hip) for kernels wider than K1's halo: directional units, a
-// threshold > 0 (with the -w capture on as well: head units hand their
+// K1w (wide.hip) for kernels wider than K1's halo: a threshold > 0 (directional
+// units with the -w capture on as well: head units hand their
 // retirements over from the K0 head replay, wide_profile_kernel gives the
-// dense rest), and a window of at most 65,535 cells (bw <= kMaxWideBw): the reference counts
+// dense rest; nondirectional units only with the capture off, and only inside
+// the blocking up_run -- wide_nd_mode), and a window of at most 65,535 cells
+// (bw <= kMaxWideBw): the reference counts
 // the cells add() retires in a UShort (misc/peakcall.cpp:172-177), so from
 // bw 32,768 on a gap of 2bw + 1 or more retires (gap mod 65,536) cells, the
 // rest of the window stays misaligned and a flush leaks into the buffer's
 // next unit -- only the whole-buffer replay models that (emulate.hip);
-// UNIPEAK_WIDE=0: the replay instead
+// UNIPEAK_WIDE=0: the replay instead; UNIPEAK_WIDE_ND=0 (read at up_open):
+// the replay for nondirectional units only
 static bool wide_mode(const up_ctx *c) {
     static const bool on = [] {
         const char *e = getenv("UNIPEAK_WIDE");
         return !(e && *e == '0');
     }();
-    return on && c->p.bw > kMaxBw && c->p.bw <= kMaxWideBw && kTB == 2 && c->p.region_thr > 0 && !c->p.nondir;
+    return on && c->p.bw > kMaxBw && c->p.bw <= kMaxWideBw && kTB == 2 && c->p.region_thr > 0 &&
+           (!c->p.nondir || (c->wide_nd && !c->prof_capture));
 }
+
+// K1w over both strands: its passes run only inside the blocking up_run
+// (run_wide_nd, as K1q's inside run_q11); up_run_async and the dense profile
+// of these units stay refused
+static bool wide_nd_mode(const up_ctx *c) { return c->p.nondir && wide_mode(c); }
 
 static bool replay_mode(const up_ctx *c) {
     return (c->p.bw > kMaxBw && !wide_mode(c)) || (!(c->p.region_thr > 0) && !q11_mode(c));
@@ -1693,6 +1724,7 @@ static int check_runnable(up_ctx *c, bool profile = false) {
     if (replay_mode(c)) return UP_E_UNSUPPORTED;
     // (the dense profile's window is K1's, or wide_profile_kernel's where K1w runs)
     if (profile && c->p.bw > kMaxBw && !wide_mode(c)) return UP_E_UNSUPPORTED;
+    if (wide_nd_mode(c) && (profile || !c->wide_nd_run)) return UP_E_UNSUPPORTED;
     return q11_mode(c) && !c->q11_run && !profile ? UP_E_UNSUPPORTED : UP_OK;
 }
 
@@ -2174,6 +2206,26 @@ static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatPar
                        c->hp_status[slot].dev, thdr);
     HIPCHK(hipGetLastError());
     if (events) HIPCHK(hipEventRecord(ps.ev[3], ps.stream));
+    if (P.corr_in) {  // -D -y behind K1w: strandCorr(0) of every region (wide.hip), K3 takes it
+                      // (timed with K3: up_timings [2])
+        const unsigned blocks = wide_corr_blocks(c);
+        const size_t lds = corr_lds_bytes(c->p.bw);
+        const uint32_t lcap = wide_list_cap();
+        const int pm = pool_mode(c);
+        if (pm == 0)
+            hipLaunchKernelGGL(wide_corr_kernel<0>, dim3(blocks), dim3(64), lds, ps.stream, SP, ps.d_starts.p,
+                               ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, (uint64_t)cap, ps.d_wslab.p, lcap,
+                               ps.d_wcorr.p);
+        else if (pm == 1)
+            hipLaunchKernelGGL(wide_corr_kernel<1>, dim3(blocks), dim3(64), lds, ps.stream, SP, ps.d_starts.p,
+                               ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, (uint64_t)cap, ps.d_wslab.p, lcap,
+                               ps.d_wcorr.p);
+        else
+            hipLaunchKernelGGL(wide_corr_kernel<2>, dim3(blocks), dim3(64), lds, ps.stream, SP, ps.d_starts.p,
+                               ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, (uint64_t)cap, ps.d_wslab.p, lcap,
+                               ps.d_wcorr.p);
+        HIPCHK(hipGetLastError());
+    }
     dispatch_stats(c, ps.stream, P, std::max<uint64_t>(ps.req_last_nreg, 1024));
     HIPCHK(hipGetLastError());
     if (ps.req_q11_place)
@@ -2224,7 +2276,12 @@ static int launch_pass(up_ctx *c, int slot) {
     // at most 8 resident 4-wave workgroups per CU
     const bool corr = c->p.nondir && (c->p.want_corr || c->p.corr_thr > -1);
     const uint32_t corr_cap = 1024;
-    if (corr) HIPCHK(ps.d_corr.ensure((size_t)(c->ncu > 0 ? c->ncu : 256) * 8 * 4 * corr_cap * 2));
+    const bool wcorr = corr && c->p.bw > kMaxBw;  // K1w: wide_corr_kernel instead of K3's KDE
+    if (corr && !wcorr) HIPCHK(ps.d_corr.ensure((size_t)(c->ncu > 0 ? c->ncu : 256) * 8 * 4 * corr_cap * 2));
+    if (wcorr) {
+        HIPCHK(ps.d_wcorr.ensure(cap + 1));
+        HIPCHK(ps.d_wslab.ensure((size_t)wide_corr_blocks(c) * 2 * kCorrSlab));
+    }
     if (!ps.req_target) {
         HIPCHK(c->hp_regions[slot].ensure(cap + 1));
         HIPCHK(c->hp_counts[slot].ensure((cap + 1) * S));
@@ -2274,7 +2331,8 @@ static int launch_pass(up_ctx *c, int slot) {
     P.peak_pos = ps.d_peak_pos.p;
     P.peak_val = ps.d_peak_val.p;
     P.spk = ps.d_spk.p;
-    P.corr_scratch = corr ? ps.d_corr.p : nullptr;
+    P.corr_scratch = corr && !wcorr ? ps.d_corr.p : nullptr;
+    P.corr_in = wcorr ? ps.d_wcorr.p : nullptr;
     P.corr_cap = corr_cap;
     // K3 writes the records straight into mapped pinned host memory (or the
     // caller's record target).  Staging them in device memory and delivering
@@ -2311,9 +2369,13 @@ static int launch_pass(up_ctx *c, int slot) {
             graph = false;
             const unsigned blocks = std::max(1u, std::min<uint32_t>(ns, 8192));
             const int pm = pool_mode(c);
-            if (pm == 0) hipLaunchKernelGGL(wide_kernel<0>, dim3(blocks), dim3(64), 0, s1, SP);
-            else if (pm == 1) hipLaunchKernelGGL(wide_kernel<1>, dim3(blocks), dim3(64), 0, s1, SP);
-            else hipLaunchKernelGGL(wide_kernel<2>, dim3(blocks), dim3(64), 0, s1, SP);
+            if (c->p.nondir) {
+                if (pm == 0) hipLaunchKernelGGL((wide_kernel<0, true>), dim3(blocks), dim3(64), 0, s1, SP);
+                else if (pm == 1) hipLaunchKernelGGL((wide_kernel<1, true>), dim3(blocks), dim3(64), 0, s1, SP);
+                else hipLaunchKernelGGL((wide_kernel<2, true>), dim3(blocks), dim3(64), 0, s1, SP);
+            } else if (pm == 0) hipLaunchKernelGGL((wide_kernel<0, false>), dim3(blocks), dim3(64), 0, s1, SP);
+            else if (pm == 1) hipLaunchKernelGGL((wide_kernel<1, false>), dim3(blocks), dim3(64), 0, s1, SP);
+            else hipLaunchKernelGGL((wide_kernel<2, false>), dim3(blocks), dim3(64), 0, s1, SP);
         } else {
             // K1a: stream + screen -- the chunk-sum plane when the index is
             // on, else the 2-bit fields (one-pass cost: no derived data read)
@@ -2330,6 +2392,7 @@ static int launch_pass(up_ctx *c, int slot) {
     ps.k3_kind = k3_kind_for(c, P, std::max<uint64_t>(ps.req_last_nreg, 1024));  // (dispatch_stats' arguments)
     const int k1b_kind = (ps.req_q11 || c->p.bw > kMaxBw) ? -1 : k1b_kind_for(c);  // (enqueue_rest's K1b)
     ps.k1b_kind = k1b_kind;
+    ps.scan_kind = ps.req_q11 ? 2 : c->p.bw > kMaxBw ? 1 : 0;  // (the branch taken above)
     if (!graph || tl >= 2) {
         if (int r = enqueue_rest(c, slot, SP, P, cap, kw, kx, tl >= 2)) return r;
         HIPCHK(hipEventRecord(ps.done, ps.stream));
@@ -2487,6 +2550,7 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     c->cur_slot = slot;
     c->last_k3_kind = -1;
     c->last_k1b_kind = -1;
+    c->last_scan_kind = -1;
     if (c->units.empty()) {
         ++c->seq_done;
         if (n_regions) *n_regions = 0;
@@ -2549,6 +2613,7 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     c->last_nreg = nreg;
     c->last_k3_kind = ps.k3_kind;
     c->last_k1b_kind = ps.k1b_kind;
+    c->last_scan_kind = ps.scan_kind;  // (head units' K0 chains aside)
     // (a K1q pass's head units take q11_finish's chains instead)
     int r = ps.req_q11 ? UP_OK : replay_head_hits(c, slot);
     if (r) return fail(r);
@@ -2667,6 +2732,7 @@ static int run_replay(up_ctx *c, uint64_t *n_regions) {
     c->q11_placed = false;
     c->last_k3_kind = -1;  // K0 computes the replay's statistics
     c->last_k1b_kind = -1;
+    c->last_scan_kind = c->units.empty() ? -1 : 3;
     c->h_regions.clear();
     c->h_counts.clear();
     c->h_emulated.clear();
@@ -2923,6 +2989,16 @@ static int run_q11(up_ctx *c, uint64_t *n_regions) {
     return UP_OK;
 }
 
+// K1w over a nondirectional context: one blocking pass (check_runnable
+// admits it only here)
+static int run_wide_nd(up_ctx *c, uint64_t *n_regions) {
+    c->wide_nd_run = true;
+    int r = up_run_async(c);
+    if (!r) r = up_run_wait(c, n_regions);
+    c->wide_nd_run = false;
+    return r;
+}
+
 int up_run(up_ctx *c, uint64_t *n_regions) {
     if (!c) return UP_E_ARG;
     if (busy(c)) return UP_E_STATE;
@@ -2930,6 +3006,7 @@ int up_run(up_ctx *c, uint64_t *n_regions) {
     if (rc) return rc;
     if (replay_mode(c)) return run_replay(c, n_regions);
     if (q11_mode(c)) return run_q11(c, n_regions);
+    if (wide_nd_mode(c)) return run_wide_nd(c, n_regions);
     int r = up_run_async(c);
     if (r) return r;
     return up_run_wait(c, n_regions);
@@ -3079,6 +3156,11 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
     }
     // global slab space only for regions whose scores do not stay in K4's
     // LDS: replayed ones (their stored scores are copied in) and long ones
+    // (the last pass ran K1w: K4's own KDE spans NH <= 8 window words, so
+    // wide_fill_kernel forms the scores of its regions into the slab first --
+    // mark 2; head-replayed regions keep their stored scores)
+    const bool wide = c->last_scan_kind == 1;
+    bool any_fill = false;
     std::vector<uint64_t> off(n, 0);
     std::vector<uint8_t> pref(n + 1, 0);
     uint64_t tot = 0;
@@ -3087,6 +3169,10 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
         const uint64_t len = (uint64_t)en[idx[j]] - st[idx[j]] + 1;
         pref[j] = c->q11_placed ? (qrep.count(idx[j]) ? 1 : 0)
                                 : (c->host_regions && c->h_emulated[idx[j]] == 1 ? 1 : 0);
+        if (wide && !pref[j]) {
+            pref[j] = 2;
+            any_fill = true;
+        }
         if (pref[j] || len > (uint64_t)kShiftLds) {
             off[j] = tot;
             tot += 2ull * len;
@@ -3106,7 +3192,7 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
     HIPCHK(hipMemcpyAsync(d_idx, idx, n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_off, off.data(), n * 8, hipMemcpyHostToDevice, c->stream));
     for (size_t j = 0; j < n; ++j) {
-        if (!pref[j]) continue;
+        if (pref[j] != 1) continue;
         const uint64_t so = c->q11_placed ? qrep[idx[j]] : c->h_score_off[idx[j]];
         if (so == ~0ull) return UP_E_INTERNAL;
         const uint64_t len = (uint64_t)en[idx[j]] - st[idx[j]] + 1;
@@ -3117,6 +3203,22 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
     StatParams P = stat_params(c, ps);
     const size_t lds = kShiftLdsBytes;
     const unsigned blocks = (unsigned)std::min<size_t>(n, 8192);
+    if (any_fill) {  // the dense (f, r) of the K1w regions among the requested ones
+        ScanParams SP = scan_params(c, ps, c->ovf_cap);  // (units, pooling and kernel weights only)
+        const size_t wl = corr_lds_bytes(c->p.bw);
+        const uint32_t nn = (uint32_t)n, lcap = wide_list_cap();
+        const int pm = pool_mode(c);
+        if (pm == 0)
+            hipLaunchKernelGGL(wide_fill_kernel<0>, dim3(blocks), dim3(64), wl, c->stream, SP, ps.d_starts.p,
+                               ps.d_ends.p, ps.d_runit.p, d_idx, nn, d_off, d_pref, d_slab, lcap);
+        else if (pm == 1)
+            hipLaunchKernelGGL(wide_fill_kernel<1>, dim3(blocks), dim3(64), wl, c->stream, SP, ps.d_starts.p,
+                               ps.d_ends.p, ps.d_runit.p, d_idx, nn, d_off, d_pref, d_slab, lcap);
+        else
+            hipLaunchKernelGGL(wide_fill_kernel<2>, dim3(blocks), dim3(64), wl, c->stream, SP, ps.d_starts.p,
+                               ps.d_ends.p, ps.d_runit.p, d_idx, nn, d_off, d_pref, d_slab, lcap);
+        HIPCHK(hipGetLastError());
+    }
     {
         const void *k = shift_kernel_for(P.bw, pool_mode(c));
         uint32_t nn = (uint32_t)n;
@@ -3167,10 +3269,7 @@ int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t cou
     P.prof_unit = unit;
     HIPCHK(hipEventRecord(c->ev[5], c->stream));
     if (c->p.bw > kMaxBw) {  // wide_mode (check_runnable): the planes are current (want_index)
-        static const uint32_t cap = [] {  // UNIPEAK_WIDE_PROFILE_LIST=0: the direct window walk (A/B)
-            const char *e = getenv("UNIPEAK_WIDE_PROFILE_LIST");
-            return e && *e == '0' ? 0u : (uint32_t)kProfHits;
-        }();
+        const uint32_t cap = wide_list_cap();
         const uint64_t nstretch = ((first + count - 2) / 64 - (first - 1) / 64) / kProfWords + 1;
         const dim3 grid((unsigned)std::min<uint64_t>(nstretch, 1u << 16));
         const size_t lds = prof_lds_bytes(c->p.bw);

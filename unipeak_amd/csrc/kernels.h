@@ -206,6 +206,8 @@ struct StatParams {
     int32_t cut;          // measurement aid (UNIPEAK_K3L_CUT): K3L stops after phase `cut` (wrong records)
     int32_t heavy;        // K3L: regions with more hits take the wave's kurtosis path (UNIPEAK_K3L_HEAVY)
     int32_t w2hits;       // K3L second walk: 1 = four hits per step, 0 = 16 fields per dword (UNIPEAK_K3L_W2)
+    const double *corr_in; // -D -y behind K1w: strandCorr(0) per region (wide_corr_kernel), or null --
+                           // set: K3 keeps K1w's peaks, runs no KDE of its own and takes corr from it
 };
 
 }  // namespace upk

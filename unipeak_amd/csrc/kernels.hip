@@ -2696,7 +2696,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UPK_K3
 
     // K1 saw the whole run: its peak is known and, unless the strand
     // correlation is wanted, no score is needed here -- only the counts
-    const bool known = P.peak_pos != nullptr && !(NONDIR && P.want_corr);
+    // (K1w: the correlation arrives in corr_in -- this kernel's KDE spans
+    // NH <= 8 window words and must not run for a wider kernel)
+    const bool known = P.peak_pos != nullptr && !(NONDIR && P.want_corr && !P.corr_in);
     // Region descriptors (start, end, unit, peak position, peak value) come
     // one region ahead: lanes 0..5 read the next region's six words with one
     // vector load at the top of an iteration, and with one pooled directional
@@ -3268,7 +3270,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UPK_K3
         // ---- pass 3: strandCorr(0) (data.cpp:38-58, 184-193) ----
         const uint32_t n = right - left + 1;
         double corr = __builtin_nan("");
-        if (NONDIR && P.want_corr && n > 3) {
+        if (NONDIR && P.want_corr && P.corr_in) {
+            corr = P.corr_in[ri];  // wide_corr_kernel: the same sums over K1w's dense scores
+        } else if (NONDIR && P.want_corr && n > 3) {
             const double m1 = sf / (double)n, m2 = sr / (double)n;
             double ss1 = 0.0, ss2 = 0.0, ssr = 0.0;
             const bool cached = cslab && (uint64_t)n + 63 <= P.corr_cap;

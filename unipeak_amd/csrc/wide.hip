@@ -5,38 +5,46 @@
 // replay runs instead; the reference's -b itself is a UShort,
 // misc/kernel.hpp:16).  #included by api.hip.
 //
-// One wave per strip (16,384 positions), directional units with a threshold
-// > 0, as K1 (screen + exact) in one kernel:
+// One wave per strip (16,384 positions), units with a threshold > 0, as K1
+// (screen + exact) in one kernel:
 //  * screen: the strip's window of chunk sums of its screen plane (the one
-//    pooled track's plane, or the unit's weighted pooled plane; a saturated
+//    pooled track's plane, or the unit's weighted pooled plane -- always the
+//    pooled plane for a nondirectional unit: it sums both strands; a saturated
 //    255 counts as unbounded) as prefix sums in LDS; a 64-position word can
 //    hold a flag only if the weighted tag sum over the union of its
 //    positions' windows, [x0 - bw, x0 + 63 + bw], exceeds the budget wskip
-//    (the same bound K1a uses);
+//    (the same bound K1a uses; it bounds forwardScore + reverseScore as well);
 //  * exact: for each such word every lane sums its position's score over the
 //    adds of that window in ascending position -- the order the reference's
 //    deque cell receives them (peakcall.cpp:186-209) -- as kern[x - a + bw] *
 //    countSum in FP64 (the pooled count words come from load_words, so
 //    pooled samples, coefficients and the pooled count track behave as in
-//    K1b);
+//    K1b); a nondirectional unit (NONDIR) keeps one such sum per strand and
+//    flags forwardScore + reverseScore (peakcall.cpp:57, 207-209);
 //  * runs, peaks (first maximum) and the strip's record list and edge flags
 //    exactly as K1b writes them, so K2 and K3 (known peaks) follow unchanged.
 // The tracks of every unit are padded past len + 2bw (unit_stride), so the
 // window loads of positions up to len + bw stay in bounds.
 //
-// wide_profile_kernel (below): the dense FP64 profile of such a unit, the
-// same ascending sums for every position of a range (up_unit_profile*, -w).
+// wide_stretch_scores (below): the dense FP64 scores of one strand over a
+// stretch of 64 words, the same ascending sums; its users are
+//  * wide_profile_kernel: the dense profile of a directional unit
+//    (up_unit_profile*, -w);
+//  * wide_corr_kernel: strandCorr(0) of every region of a nondirectional
+//    pass, between K2 and K3 (K3's own KDE spans NH <= 8 window words);
+//  * wide_fill_kernel: the (f, r) slabs of requested regions for K4
+//    (up_shift_scan, up_shift_best).
 
 namespace upk {
 
 constexpr uint32_t kWideSat = 1u << 18;  // a saturated chunk in the prefix sums
 constexpr int kWideChunks = (kStrip + 2 * kMaxWideBw + 64) / 16 + 4;  // 5,127: the widest strip window
 
-// the score of position x0 + lane: the adds of [x0 - bw, x0 + 63 + bw] in
-// ascending position, the window reloaded word by word (K1w's exact walk and
-// the profile kernel's fallback)
+// the score of position x0 + lane on one strand: the adds of [x0 - bw,
+// x0 + 63 + bw] in ascending position, the window reloaded word by word
+// (K1w's exact walk and the dense scores' fallback)
 template <int POOL>
-__device__ __forceinline__ double wide_word_score(const ScanParams &P, const UnitDesc &U, int S, int bw,
+__device__ __forceinline__ double wide_word_score(const ScanParams &P, const UnitDesc &U, int S, int strand, int bw,
                                                   int64_t x0, int lane) {
     const int64_t x = x0 + lane;
     double f = 0.0;
@@ -44,7 +52,7 @@ __device__ __forceinline__ double wide_word_score(const ScanParams &P, const Uni
     for (int64_t wb = wb0; wb <= x0 + 63 + bw; wb += 64) {
         if (wb + 63 < 1 || wb > (int64_t)U.len) continue;  // no adds outside 1 .. len
         WinT<POOL> cs[1];
-        load_words<1, POOL>(cs, U, S, 0, wb, lane, P.nnc, P.nc, P.coef);
+        load_words<1, POOL>(cs, U, S, strand, wb, lane, P.nnc, P.nc, P.coef);
         uint64_t m = __ballot(nz(cs[0]) && wb + lane >= 1 && wb + lane <= (int64_t)U.len);
         while (m) {
             const int k = __builtin_ctzll(m);
@@ -58,7 +66,34 @@ __device__ __forceinline__ double wide_word_score(const ScanParams &P, const Uni
     return f;
 }
 
-template <int POOL>
+// prefix sums of the chunk sums c0 .. c0 + nch - 1 of plane pl (chunks outside
+// the track count 0, a saturated one kWideSat) into pre[0 .. nch]; the block
+// is one wave
+__device__ __forceinline__ void wide_prefix(gu8 *pl, int64_t nchunk_track, int64_t c0, int nch, uint32_t *pre,
+                                            int lane) {
+    __syncthreads();  // the previous window's readers are done
+    if (lane == 0) pre[0] = 0u;
+    uint32_t carry = 0;
+    for (int base = 0; base < nch; base += 64) {
+        const int i = base + lane;
+        const int64_t c = c0 + i;
+        uint32_t v = 0;
+        if (i < nch && c >= 0 && c < nchunk_track) {
+            v = pl[c];
+            v = v == 255u ? kWideSat : v;
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = (uint32_t)__shfl_up((int)v, o);
+            if (lane >= o) v += y;
+        }
+        if (i < nch) pre[i + 1] = carry + v;
+        carry += (uint32_t)__shfl((int)v, 63);
+    }
+    __syncthreads();
+}
+
+template <int POOL, bool NONDIR>
 __global__ void __launch_bounds__(64) wide_kernel(ScanParams P) {
     __shared__ uint32_t pre[kWideChunks + 1];
     const int lane = threadIdx.x;
@@ -71,31 +106,12 @@ __global__ void __launch_bounds__(64) wide_kernel(ScanParams P) {
         const int64_t p0 = 1 + (int64_t)local * kStrip, pend = p0 + kStrip - 1;
         const int64_t dom_end = (int64_t)U.len + bw;  // the last position a flush retires
         // ---- screen: prefix sums of the window's chunk sums ----
-        gu8 *pl = POOL == 0 ? plane_u8(U, S, 0, P.nc[0]) : pooled_u8(U, S);
+        gu8 *pl = (POOL == 0 && !NONDIR) ? plane_u8(U, S, 0, P.nc[0]) : pooled_u8(U, S);
         const int64_t nchunk_track = (int64_t)(U.stride / 4);
         const int64_t c0 = (kPadPos + (p0 - bw) - 1) >> 4;  // (arithmetic shift: floor)
         const int64_t c1 = (kPadPos + (pend + bw) - 1) >> 4;
         const int nch = (int)(c1 - c0 + 1);
-        __syncthreads();  // the previous strip's readers are done
-        if (lane == 0) pre[0] = 0u;
-        uint32_t carry = 0;
-        for (int base = 0; base < nch; base += 64) {
-            const int i = base + lane;
-            const int64_t c = c0 + i;
-            uint32_t v = 0;
-            if (i < nch && c >= 0 && c < nchunk_track) {
-                v = pl[c];
-                v = v == 255u ? kWideSat : v;
-            }
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t y = (uint32_t)__shfl_up((int)v, o);
-                if (lane >= o) v += y;
-            }
-            if (i < nch) pre[i + 1] = carry + v;
-            carry += (uint32_t)__shfl((int)v, 63);
-        }
-        __syncthreads();
+        wide_prefix(pl, nchunk_track, c0, nch, pre, lane);
         // candidate words: lane l decides words l, l + 64, l + 128, l + 192
         uint64_t cand[4];
 #pragma unroll
@@ -127,7 +143,11 @@ __global__ void __launch_bounds__(64) wide_kernel(ScanParams P) {
                 continue;
             }
             const int64_t x = x0 + lane;
-            const double f = wide_word_score<POOL>(P, U, S, bw, x0, lane);
+            double f = wide_word_score<POOL>(P, U, S, 0, bw, x0, lane);
+            if constexpr (NONDIR) {  // forwardScore + reverseScore, each its own ascending sum
+                const double r = wide_word_score<POOL>(P, U, S, 1, bw, x0, lane);
+                f = f + r;
+            }
             const bool flag = x <= dom_end && f >= P.thr;
             const uint64_t F = __ballot(flag);
             if (g == 0) F0 = F;
@@ -175,27 +195,26 @@ __global__ void __launch_bounds__(64) wide_kernel(ScanParams P) {
     }
 }
 
-// ---- the dense profile of a wide kernel (up_unit_profile*, bin/regions -w) ----
-// FP64 scores of positions [prof_first, prof_first + prof_len) of unit
-// prof_unit into the pre-zeroed prof_f (directional units only: prof_r stays
-// zero), each the ascending sum K1w forms.  One wave owns a stretch of
-// kProfWords words:
-//  * screen: K1w's prefix sums of the stretch window's chunk sums; a word
-//    whose union window holds no tag at all (a saturated chunk counts as
-//    tags) keeps its 0.0 -- "no tags", not wskip: a profile needs every
-//    nonzero score;
-//  * gather: nearly every word of a profile is live, so the window is not
-//    reloaded per word -- the hits (position, pooled count as FP64) of the
-//    live words' windows are listed once, ascending, in LDS (load words whose
+// ---- dense scores of a wide kernel: one strand over a stretch of words ----
+// A stretch is up to kProfWords words of 64 positions from x_lo (64-aligned
+// + 1), owned by one wave (the block):
+//  * screen (wide_stretch_screen): K1w's prefix sums of the stretch window's
+//    chunk sums; a word whose union window holds no tag at all (a saturated
+//    chunk counts as tags) scores 0.0 -- "no tags", not wskip: the dense
+//    scores need every nonzero one.  The pooled plane of a nondirectional
+//    unit holds both strands' tags, so one screen serves both strands;
+//  * gather: nearly every word is live, so the window is not reloaded per
+//    word -- the strand's hits (position, pooled count as FP64) of the live
+//    words' windows are listed once, ascending, in LDS (load words whose
 //    four chunks are empty are not loaded at all);
 //  * walk: every live word adds the list's sub-range [x0 - bw, x0 + 63 + bw]
 //    (two cursors that only move forward), one multiply and one add per hit
 //    and lane, in list order = ascending position;
-//  * a stretch whose windows hold more than `cap` (<= kProfHits) hits walks
-//    every live word with wide_word_score instead (cap 0: always).
-// Positions above len + bw are never written.
+//  * a stretch whose windows hold more than `cap` (<= kProfHits) hits of the
+//    strand walks every live word with wide_word_score instead (cap 0:
+//    always) -- the same adds in the same order, so the same bits.
 constexpr int kProfWords = 64;  // one ballot of live words per stretch
-constexpr int kProfHits = 512;  // list entries per wave (12 bytes each)
+constexpr int kProfHits = 512;  // list entries per wave and strand (12 bytes each)
 __host__ __device__ constexpr int prof_chunks(int bw) { return (kProfWords * 64 + 2 * bw) / 16 + 3; }
 __host__ __device__ constexpr size_t prof_lds_bytes(int bw) {
     return (size_t)kProfHits * 12 + (((size_t)prof_chunks(bw) + 1) * 4 + 15) / 16 * 16;
@@ -204,6 +223,122 @@ __host__ __device__ constexpr size_t prof_lds_bytes(int bw) {
 __device__ __forceinline__ int64_t i64min(int64_t a, int64_t b) { return a < b ? a : b; }
 __device__ __forceinline__ int64_t i64max(int64_t a, int64_t b) { return a > b ? a : b; }
 
+// chunks [a, b] (relative to the window's first chunk, clipped to it) hold a tag
+__device__ __forceinline__ bool wide_tags(const uint32_t *pre, int nch, int64_t a, int64_t b) {
+    a = a < 0 ? 0 : a;
+    b = b > nch - 1 ? nch - 1 : b;
+    return a <= b && pre[b + 1] != pre[a];
+}
+
+struct WideScreen {
+    int64_t c0;     // the window's first chunk
+    int nch;        // its chunks (pre[0 .. nch])
+    uint64_t cand;  // the stretch's live words
+};
+
+__device__ __forceinline__ WideScreen wide_stretch_screen(gu8 *pl, int64_t nchunk_track, int bw, int64_t x_lo,
+                                                          int nw, uint32_t *pre, int lane) {
+    WideScreen W;
+    const int64_t x_hi = x_lo + 64 * nw - 1;
+    W.c0 = (kPadPos + (x_lo - bw) - 1) >> 4;  // (arithmetic shift: floor)
+    const int64_t c1 = (kPadPos + (x_hi + bw) - 1) >> 4;
+    W.nch = (int)i64min(c1 - W.c0 + 1, prof_chunks(bw));  // (c1 - c0 + 1 never exceeds it)
+    wide_prefix(pl, nchunk_track, W.c0, W.nch, pre, lane);
+    bool live = false;  // lane l decides word l
+    if (lane < nw) {
+        const int64_t x0 = x_lo + 64 * lane;
+        live = wide_tags(pre, W.nch, ((kPadPos + x0 - bw - 1) >> 4) - W.c0, ((kPadPos + x0 + 63 + bw - 1) >> 4) - W.c0);
+    }
+    W.cand = __ballot(live);
+    return W;
+}
+
+// store(x, f) for position x = x0 + lane of every live word of the stretch
+// (ALL: of its other words too, with 0.0); hcnt / hpos: this strand's list
+template <int POOL, bool ALL, class Store>
+__device__ __forceinline__ void wide_stretch_scores(const ScanParams &P, const UnitDesc &U, int S, int strand, int bw,
+                                                    int64_t x_lo, int nw, const WideScreen &W, const uint32_t *pre,
+                                                    uint32_t cap, double *hcnt, uint32_t *hpos, int lane,
+                                                    Store store) {
+    const uint64_t cand = W.cand;
+    const uint64_t below = lane == 0 ? 0ull : ~0ull >> (64 - lane);  // the lanes before this one
+    // ---- gather: the hits of the live words' windows, ascending ----
+    uint32_t nh = 0;
+    bool listed = cap != 0 && cand != 0;
+    if (cand) {
+        const int64_t glo = i64max(1, x_lo + 64 * (int64_t)__builtin_ctzll(cand) - bw);
+        const int64_t ghi = i64min((int64_t)U.len, x_lo + 64 * (int64_t)(63 - __builtin_clzll(cand)) + 63 + bw);
+        for (int64_t wb = ((glo - 1) >> 6) * 64 + 1; listed && wb <= ghi; wb += 64 * 64) {
+            const int64_t wl = wb + 64 * lane;  // lane l decides load word l of this batch
+            const int64_t ci = ((kPadPos + wl - 1) >> 4) - W.c0;
+            uint64_t mw = __ballot(wl <= ghi && wide_tags(pre, W.nch, ci, ci + 3));
+            while (mw) {
+                const int k = __builtin_ctzll(mw);
+                mw &= mw - 1;
+                const int64_t wk = wb + 64 * k;
+                WinT<POOL> cs[1];
+                load_words<1, POOL>(cs, U, S, strand, wk, lane, P.nnc, P.nc, P.coef);
+                const bool hit = nz(cs[0]) && wk + lane >= glo && wk + lane <= ghi;
+                const uint64_t hm = __ballot(hit);
+                const uint32_t n = (uint32_t)__builtin_popcountll(hm);
+                if (nh + n > cap) {
+                    listed = false;
+                    break;
+                }
+                if (hit) {
+                    const uint32_t i = nh + (uint32_t)__builtin_popcountll(hm & below);
+                    hpos[i] = (uint32_t)(wk + lane);
+                    hcnt[i] = (double)cs[0];
+                }
+                nh += n;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- walk ----
+    uint32_t li = 0, ui = 0;  // the list's sub-range of the current word: [li, ui)
+    for (int g = 0; g < nw; ++g) {
+        const int64_t x0 = x_lo + 64 * g, x = x0 + lane;
+        if (!((cand >> g) & 1ull)) {
+            if constexpr (ALL) store(x, 0.0);
+            continue;
+        }
+        double f;
+        if (listed) {
+            const int64_t a_lo = x0 - bw, a_hi = x0 + 63 + bw;
+            for (;;) {  // (ascending list: the lanes that hold an earlier hit form a prefix)
+                const uint32_t i = li + lane;
+                const int n = __builtin_popcountll(__ballot(i < nh && (int64_t)hpos[i < nh ? i : 0] < a_lo));
+                li += n;
+                if (n < 64) break;
+            }
+            ui = ui < li ? li : ui;
+            for (;;) {
+                const uint32_t i = ui + lane;
+                const int n = __builtin_popcountll(__ballot(i < nh && (int64_t)hpos[i < nh ? i : 0] <= a_hi));
+                ui += n;
+                if (n < 64) break;
+            }
+            f = 0.0;
+#pragma unroll 4
+            for (uint32_t i = li; i < ui; ++i) {
+                const int64_t j = x - (int64_t)hpos[i] + bw;  // index of kern[x - a + bw]
+                const bool in = j >= 0 && j <= 2 * (int64_t)bw;
+                const double t = f + P.kern[in ? j : 0] * hcnt[i];
+                f = in ? t : f;
+            }
+        } else {
+            f = wide_word_score<POOL>(P, U, S, strand, bw, x0, lane);
+        }
+        store(x, f);
+    }
+}
+
+// ---- the dense profile of a wide kernel (up_unit_profile*, bin/regions -w) ----
+// FP64 scores of positions [prof_first, prof_first + prof_len) of unit
+// prof_unit into the pre-zeroed prof_f (directional units only: prof_r stays
+// zero), each the ascending sum K1w forms.  One wave owns a stretch of
+// kProfWords words.  Positions above len + bw are never written.
 template <int POOL>
 __global__ void __launch_bounds__(64) wide_profile_kernel(ScanParams P, uint32_t cap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char prof_lds[];
@@ -221,115 +356,167 @@ __global__ void __launch_bounds__(64) wide_profile_kernel(ScanParams P, uint32_t
     const int64_t nstretch = (w_last - w_first) / kProfWords + 1;
     gu8 *pl = POOL == 0 ? plane_u8(U, S, 0, P.nc[0]) : pooled_u8(U, S);
     const int64_t nchunk_track = (int64_t)(U.stride / 4);
-    const uint64_t below = lane == 0 ? 0ull : ~0ull >> (64 - lane);  // the lanes before this one
     for (int64_t s = blockIdx.x; s < nstretch; s += gridDim.x) {
         const int64_t w0 = w_first + s * kProfWords;
         const int nw = (int)i64min(kProfWords, w_last - w0 + 1);
-        const int64_t x_lo = 1 + 64 * w0, x_hi = x_lo + 64 * nw - 1;
-        // ---- screen: prefix sums of the window's chunk sums (as K1w) ----
-        const int64_t c0 = (kPadPos + (x_lo - bw) - 1) >> 4;  // (arithmetic shift: floor)
-        const int64_t c1 = (kPadPos + (x_hi + bw) - 1) >> 4;
-        const int nch = (int)i64min(c1 - c0 + 1, prof_chunks(bw));  // (c1 - c0 + 1 never exceeds it)
-        __syncthreads();  // the previous stretch's readers are done
-        if (lane == 0) pre[0] = 0u;
-        uint32_t carry = 0;
-        for (int base = 0; base < nch; base += 64) {
-            const int i = base + lane;
-            const int64_t c = c0 + i;
-            uint32_t v = 0;
-            if (i < nch && c >= 0 && c < nchunk_track) {
-                v = pl[c];
-                v = v == 255u ? kWideSat : v;
+        const int64_t x_lo = 1 + 64 * w0;
+        const WideScreen W = wide_stretch_screen(pl, nchunk_track, bw, x_lo, nw, pre, lane);
+        if (!W.cand) continue;
+        wide_stretch_scores<POOL, false>(P, U, S, 0, bw, x_lo, nw, W, pre, cap, hcnt, hpos, lane,
+                                         [&](int64_t x, double f) {
+                                             const int64_t q = x - P.prof_first;
+                                             if (q >= 0 && q < (int64_t)P.prof_len && x <= dom_end) P.prof_f[q] = f;
+                                         });
+    }
+}
+
+// ---- both strands' dense scores of a position range (nondirectional) ----
+// LDS of wide_corr_kernel / wide_fill_kernel: a hit list per strand, the
+// 64 x 3 products of the correlation's sequential sums, the prefix sums
+constexpr int kCorrSlab = kProfWords * 64;  // positions of one wave's global (f, r) slab: a stretch
+__host__ __device__ constexpr size_t corr_lds_bytes(int bw) {
+    return 2 * (size_t)kProfHits * 12 + 64 * 3 * 8 + (((size_t)prof_chunks(bw) + 1) * 4 + 15) / 16 * 16;
+}
+struct WideLds {
+    double *hcnt[2];
+    double *prod;
+    uint32_t *hpos[2];
+    uint32_t *pre;
+};
+__device__ __forceinline__ WideLds wide_lds(unsigned char *lds) {
+    WideLds L;
+    L.hcnt[0] = (double *)lds;
+    L.hcnt[1] = L.hcnt[0] + kProfHits;
+    L.prod = L.hcnt[1] + kProfHits;
+    L.hpos[0] = (uint32_t *)(L.prod + 64 * 3);
+    L.hpos[1] = L.hpos[0] + kProfHits;
+    L.pre = L.hpos[1] + kProfHits;
+    return L;
+}
+
+// forwardScore and reverseScore of positions a .. b (1 <= a <= b) of unit U ->
+// of[x - a], orr[x - a]: every position is written, each score the ascending
+// sum the reference's Region::scores holds; block-wide visible on return
+template <int POOL>
+__device__ __forceinline__ void wide_range_scores(const ScanParams &P, const UnitDesc &U, int S, int bw, int64_t a,
+                                                  int64_t b, double *of, double *orr, const WideLds &L, uint32_t cap,
+                                                  int lane) {
+    gu8 *pl = pooled_u8(U, S);
+    const int64_t nchunk_track = (int64_t)(U.stride / 4);
+    const int64_t w_first = (a - 1) >> 6, w_last = (b - 1) >> 6;
+    for (int64_t w0 = w_first; w0 <= w_last; w0 += kProfWords) {
+        const int nw = (int)i64min(kProfWords, w_last - w0 + 1);
+        const int64_t x_lo = 1 + 64 * w0;
+        const WideScreen W = wide_stretch_screen(pl, nchunk_track, bw, x_lo, nw, L.pre, lane);
+        wide_stretch_scores<POOL, true>(P, U, S, 0, bw, x_lo, nw, W, L.pre, cap, L.hcnt[0], L.hpos[0], lane,
+                                        [&](int64_t x, double f) {
+                                            if (x >= a && x <= b) of[x - a] = f;
+                                        });
+        wide_stretch_scores<POOL, true>(P, U, S, 1, bw, x_lo, nw, W, L.pre, cap, L.hcnt[1], L.hpos[1], lane,
+                                        [&](int64_t x, double r) {
+                                            if (x >= a && x <= b) orr[x - a] = r;
+                                        });
+    }
+    __syncthreads();  // (global slab writes: visible to the wave's other lanes)
+}
+
+// ---- strandCorr(0) of every region of a wide nondirectional pass ----
+// Between K2 and K3, one wave per region [left, right] of starts / ends:
+// Region::strandCorr(0) (misc/data.cpp:38-58, 184-193) over the dense f and r
+// with exactly the arithmetic of K3's pass 3 -- sequential sums for the two
+// means, then sequential sums of d1*d1, d2*d2 and d1*d2, sqrt(ss / (n - 1)),
+// NaN for n <= 3 -- one double per region into `out`; K3 then takes it
+// (StatParams::corr_in) instead of running its own KDE.
+// Memory: one slab of kCorrSlab (f, r) positions per wave, whatever the
+// regions hold; a region that fits keeps its scores for the second pass, a
+// longer one forms them again slab by slab (the same sums, so the same bits).
+template <int POOL>
+__global__ void __launch_bounds__(64) wide_corr_kernel(ScanParams P, const uint32_t *starts, const uint32_t *ends,
+                                                       const uint32_t *reg_unit, const uint64_t *nreg_p,
+                                                       uint64_t reg_cap, double *slabs, uint32_t cap, double *out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char corr_lds[];
+    const WideLds L = wide_lds(corr_lds);
+    const int lane = threadIdx.x;
+    const int bw = P.bw;
+    const int S = P.S;
+    const uint64_t nreg = *nreg_p < reg_cap ? *nreg_p : reg_cap;
+    double *sf_ = slabs + (uint64_t)blockIdx.x * 2 * kCorrSlab, *sr_ = sf_ + kCorrSlab;
+    for (uint64_t ri = blockIdx.x; ri < nreg; ri += gridDim.x) {
+        const uint32_t left = starts[ri], right = ends[ri];
+        const UnitDesc U = P.units[reg_unit[ri]];
+        const uint32_t n = right - left + 1;
+        double corr = __builtin_nan("");
+        if (n > 3) {
+            const bool one = n <= (uint32_t)kCorrSlab;  // the slab keeps the whole region
+            double sf = 0.0, sr = 0.0;  // sequential sums of f and r (the means)
+            for (int64_t a = left; a <= (int64_t)right; a += kCorrSlab) {
+                const int64_t b = i64min(right, a + kCorrSlab - 1);
+                wide_range_scores<POOL>(P, U, S, bw, a, b, sf_, sr_, L, cap, lane);
+                for (int64_t x0 = a; x0 <= b; x0 += 64) {
+                    const int nvalid = (int)i64min(64, b - x0 + 1);
+                    if (lane < nvalid) {
+                        L.prod[2 * lane] = sf_[x0 - a + lane];
+                        L.prod[2 * lane + 1] = sr_[x0 - a + lane];
+                    }
+                    __syncthreads();
+                    for (int l = 0; l < nvalid; ++l) {  // (wave-uniform LDS broadcasts)
+                        sf = sf + L.prod[2 * l];
+                        sr = sr + L.prod[2 * l + 1];
+                    }
+                    __syncthreads();  // prod reused by the next word
+                }
             }
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t y = (uint32_t)__shfl_up((int)v, o);
-                if (lane >= o) v += y;
+            const double m1 = sf / (double)n, m2 = sr / (double)n;
+            double ss1 = 0.0, ss2 = 0.0, ssr = 0.0;
+            for (int64_t a = left; a <= (int64_t)right; a += kCorrSlab) {
+                const int64_t b = i64min(right, a + kCorrSlab - 1);
+                if (!one) wide_range_scores<POOL>(P, U, S, bw, a, b, sf_, sr_, L, cap, lane);
+                for (int64_t x0 = a; x0 <= b; x0 += 64) {
+                    const int nvalid = (int)i64min(64, b - x0 + 1);
+                    if (lane < nvalid) {
+                        const double d1 = sf_[x0 - a + lane] - m1, d2 = sr_[x0 - a + lane] - m2;
+                        L.prod[3 * lane] = d1 * d1;
+                        L.prod[3 * lane + 1] = d2 * d2;
+                        L.prod[3 * lane + 2] = d1 * d2;
+                    }
+                    __syncthreads();
+                    for (int l = 0; l < nvalid; ++l) {
+                        ss1 = ss1 + L.prod[3 * l];
+                        ss2 = ss2 + L.prod[3 * l + 1];
+                        ssr = ssr + L.prod[3 * l + 2];
+                    }
+                    __syncthreads();
+                }
             }
-            if (i < nch) pre[i + 1] = carry + v;
-            carry += (uint32_t)__shfl((int)v, 63);
+            const double sd1 = sqrt(ss1 / ((double)n - 1));
+            const double sd2 = sqrt(ss2 / ((double)n - 1));
+            corr = ssr / (((double)n - 1) * sd1 * sd2);
+            __syncthreads();  // the slab's readers are done before the next region fills it
         }
-        __syncthreads();
-        // chunks [a, b] (relative to c0, clipped to the window) hold a tag
-        auto tags = [&](int64_t a, int64_t b) {
-            a = a < 0 ? 0 : a;
-            b = b > nch - 1 ? nch - 1 : b;
-            return a <= b && pre[b + 1] != pre[a];
-        };
-        bool live = false;  // lane l decides word l
-        if (lane < nw) {
-            const int64_t x0 = x_lo + 64 * lane;
-            live = tags(((kPadPos + x0 - bw - 1) >> 4) - c0, ((kPadPos + x0 + 63 + bw - 1) >> 4) - c0);
-        }
-        const uint64_t cand = __ballot(live);
-        if (!cand) continue;
-        // ---- gather: the hits of the live words' windows, ascending ----
-        const int64_t glo = i64max(1, x_lo + 64 * (int64_t)__builtin_ctzll(cand) - bw);
-        const int64_t ghi = i64min((int64_t)U.len, x_lo + 64 * (int64_t)(63 - __builtin_clzll(cand)) + 63 + bw);
-        uint32_t nh = 0;
-        bool listed = cap != 0;
-        for (int64_t wb = ((glo - 1) >> 6) * 64 + 1; listed && wb <= ghi; wb += 64 * 64) {
-            const int64_t wl = wb + 64 * lane;  // lane l decides load word l of this batch
-            const int64_t ci = ((kPadPos + wl - 1) >> 4) - c0;
-            uint64_t mw = __ballot(wl <= ghi && tags(ci, ci + 3));
-            while (mw) {
-                const int k = __builtin_ctzll(mw);
-                mw &= mw - 1;
-                const int64_t wk = wb + 64 * k;
-                WinT<POOL> cs[1];
-                load_words<1, POOL>(cs, U, S, 0, wk, lane, P.nnc, P.nc, P.coef);
-                const bool hit = nz(cs[0]) && wk + lane >= glo && wk + lane <= ghi;
-                const uint64_t hm = __ballot(hit);
-                const uint32_t n = (uint32_t)__builtin_popcountll(hm);
-                if (nh + n > cap) {
-                    listed = false;
-                    break;
-                }
-                if (hit) {
-                    const uint32_t i = nh + (uint32_t)__builtin_popcountll(hm & below);
-                    hpos[i] = (uint32_t)(wk + lane);
-                    hcnt[i] = (double)cs[0];
-                }
-                nh += n;
-            }
-        }
-        __syncthreads();
-        // ---- walk ----
-        uint32_t li = 0, ui = 0;  // the list's sub-range of the current word: [li, ui)
-        for (uint64_t cm = cand; cm;) {
-            const int g = __builtin_ctzll(cm);
-            cm &= cm - 1;
-            const int64_t x0 = x_lo + 64 * g, x = x0 + lane;
-            double f;
-            if (listed) {
-                const int64_t a_lo = x0 - bw, a_hi = x0 + 63 + bw;
-                for (;;) {  // (ascending list: the lanes that hold an earlier hit form a prefix)
-                    const uint32_t i = li + lane;
-                    const int n = __builtin_popcountll(__ballot(i < nh && (int64_t)hpos[i < nh ? i : 0] < a_lo));
-                    li += n;
-                    if (n < 64) break;
-                }
-                ui = ui < li ? li : ui;
-                for (;;) {
-                    const uint32_t i = ui + lane;
-                    const int n = __builtin_popcountll(__ballot(i < nh && (int64_t)hpos[i < nh ? i : 0] <= a_hi));
-                    ui += n;
-                    if (n < 64) break;
-                }
-                f = 0.0;
-#pragma unroll 4
-                for (uint32_t i = li; i < ui; ++i) {
-                    const int64_t j = x - (int64_t)hpos[i] + bw;  // index of kern[x - a + bw]
-                    const bool in = j >= 0 && j <= 2 * (int64_t)bw;
-                    const double t = f + P.kern[in ? j : 0] * hcnt[i];
-                    f = in ? t : f;
-                }
-            } else {
-                f = wide_word_score<POOL>(P, U, S, bw, x0, lane);
-            }
-            const int64_t q = x - P.prof_first;
-            if (q >= 0 && q < (int64_t)P.prof_len && x <= dom_end) P.prof_f[q] = f;
-        }
+        if (lane == 0) out[ri] = corr;
+    }
+}
+
+// ---- K4's slabs of wide regions (up_shift_scan, up_shift_best) ----
+// Requested region j (idx[j]) with fill[j] == 2: its dense f and r into
+// slab + slab_off[j] as [f[0 .. len) | r[0 .. len)], which shift_kernel then
+// reads as a prefilled region.  One wave per region, grid-stride.
+template <int POOL>
+__global__ void __launch_bounds__(64) wide_fill_kernel(ScanParams P, const uint32_t *starts, const uint32_t *ends,
+                                                       const uint32_t *reg_unit, const uint64_t *idx, uint32_t n,
+                                                       const uint64_t *slab_off, const uint8_t *fill, double *slab,
+                                                       uint32_t cap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char corr_lds[];
+    const WideLds L = wide_lds(corr_lds);
+    const int lane = threadIdx.x;
+    for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
+        if (fill[j] != 2) continue;
+        const uint64_t ri = idx[j];
+        const uint32_t left = starts[ri], right = ends[ri];
+        const UnitDesc U = P.units[reg_unit[ri]];
+        const uint32_t len = right - left + 1;
+        double *fs = slab + slab_off[j];
+        wide_range_scores<POOL>(P, U, P.S, P.bw, left, right, fs, fs + len, L, cap, lane);
     }
 }
 
