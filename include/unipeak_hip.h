@@ -326,10 +326,12 @@ int up_timings(up_ctx *ctx, double *ms, int n);
 /* dense per-position score f+r of one unit (testing/-w): out[len].  K1's
  * fused profile path up to UP_MAX_PARALLEL_BW; wider kernels where K1w runs
  * (directional units, a threshold > 0, bw up to 32767): wide_profile_kernel,
- * every score the ascending sum K1w forms, out_r all zero.  Refused
- * (UP_E_UNSUPPORTED) wherever up_run takes the exact replay of every unit,
- * and for nondirectional units above UP_MAX_PARALLEL_BW (K1w finds their
- * regions, but their dense profile is not built yet). */
+ * every score the ascending sum K1w forms, out_r all zero.  Nondirectional
+ * units above UP_MAX_PARALLEL_BW: refused by default; with
+ * up_set_wide_nd_full on, the kernel's two-strand form fills out_f with
+ * forwardScore and out_r with reverseScore, each its own ascending sum (the
+ * caller adds them; out_r = NULL is UP_E_ARG there).  Refused
+ * (UP_E_UNSUPPORTED) wherever up_run takes the exact replay of every unit. */
 int up_unit_profile(up_ctx *ctx, uint32_t unit, double *out_f, double *out_r,
                     uint32_t len);
 /* -w for units the exact replay produced (K0: quirk Q1 head hits, -r <= 0
@@ -337,7 +339,9 @@ int up_unit_profile(up_ctx *ctx, uint32_t unit, double *out_f, double *out_r,
  * bw > UP_MAX_PARALLEL_BW outside K1w), whose retirements the dense KDE does not
  * reproduce.  (A K1w pass keeps running K1w with the capture on: units without
  * head hits report resync = 0 and no entries, head units the K0 head replay's
- * entries and its resync point, as K1 passes do.)  With the
+ * entries and its resync point, as K1 passes do.  Nondirectional units above
+ * UP_MAX_PARALLEL_BW: by default the capture sends them to the replay of
+ * every unit; with up_set_wide_nd_full on they keep K1w like the rest.)  With the
  * capture on before up_run, the replay records every processPosition() with
  * a nonzero score (misc/peakcall.cpp:80-83: profileOut_->write), and
  * up_unit_replay_profile returns them for one unit in emission order:
@@ -356,6 +360,17 @@ int up_unit_replay_profile(up_ctx *ctx, uint32_t unit, uint32_t *resync, uint64_
  * NULL for directional units */
 int up_unit_profile_range(up_ctx *ctx, uint32_t unit, uint64_t first, uint32_t count,
                           double *out_f, double *out_r);
+/* nondirectional units above UP_MAX_PARALLEL_BW (bw 512..32767, threshold > 0):
+ * 0 (default): K1w only inside the blocking up_run with the -w capture off;
+ *    up_run_async and up_unit_profile* refused, the capture keeps the replay.
+ * 1: K1w also with the capture on, up_unit_profile* served by the profile
+ *    kernel, up_run_async admitted (each pass slot in flight then holds its own
+ *    64 MB of strand-correlation slabs when the correlation is evaluated).
+ * UP_E_STATE while a pass is in flight. UNIPEAK_WIDE_ND=0 still forces the
+ * replay whatever this says; a threshold <= 0 and bw >= 32768 keep the replay
+ * and the refusals as well.  The records and the -w profile do not depend on
+ * it; bin/regions sets it.  Making 1 the default is a later change. */
+int up_set_wide_nd_full(up_ctx *ctx, int on);
 
 /* ---- tags_in_regions (src/tags_in_regions.cpp:131-199) on the GPU ---------
  * A stream is one sample's alignment records in the order the reference's

@@ -19,12 +19,21 @@ score) pairs, so two libraries can be compared byte for byte.
   UNIPEAK_WIDE_PROFILE_LIST=0 ... --out direct.jsonl   (the direct window walk)
   python tools/time_wide_profile.py --check parent.jsonl new.jsonl
 
+  --nondir: the contig as ONE nondirectional synthetic unit (both strands in
+  one buffer, the unit tools/wide_nd_time.py builds, `-D -y` thresholds), the
+  capture on and, where the library has it, up_set_wide_nd_full on: a library
+  without it replays the whole buffer with the capture on; this one runs K1w
+  and wide_profile_kernel<POOL, true>.  The profile is f + r.  `--warmup`
+  passes (up_run + profile) go untimed, then `--reps` timed ones: the row
+  holds their median, minimum and maximum.
+
 Run each library in a process of its own, every step under its own
 `timeout`, the steps chained with `&&`."""
 import argparse
 import hashlib
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -37,7 +46,7 @@ FLUSH = 0xFFFFFFFF  # UP_FLUSH_EVENT
 CHUNK = 1 << 22
 
 
-def collect(g, u, length, bw, clock):
+def collect(g, u, length, bw, clock, nondir=False):
     """nonzero (pos, score) of unit u in position order; adds the C-ABI time
     to clock["profile"] and the dense kernel's to clock["kernel"]"""
     t0 = time.perf_counter()
@@ -50,8 +59,10 @@ def collect(g, u, length, bw, clock):
         while first <= end:
             n = min(CHUNK, end - first + 1)
             t0 = time.perf_counter()
-            f, _ = g.profile_range(u, first, n)
+            f, r = g.profile_range(u, first, n)
             clock["profile"] += time.perf_counter() - t0
+            if nondir:
+                f = f + r
             clock["kernel"] += g.profile_kernel_ms()
             clock["dense"] += n
             nz = np.flatnonzero(f)
@@ -102,6 +113,49 @@ def measure(capi, name, ci, length, bw, reps):
         return best
 
 
+def measure_nondir(capi, name, ci, length, bw, reps, warmup):
+    with capi.Lib(0) as g:
+        g.set_params(bw, 1, 0.0029, nondir=True)
+        u = g.add_unit(length)
+        tags = 0
+        for st in (0, 1):
+            g.synth(u, st, 0, 1, ci, st, nondir=True, peaks=True)
+            tags += g.tag_total(u, st, 0)
+        g.set_params(bw, 1, tags / length, region_thr=25.0, kurt_thr=0.0, corr_thr=0.3, hit_thr=10.0,
+                     nondir=True, want_corr=True)
+        full = hasattr(g.L, "up_set_wide_nd_full")
+        if full:
+            g.set_wide_nd_full(True)
+        g.set_profile_capture(True)
+        rows = []
+        for i in range(warmup + reps):
+            clock = {"profile": 0.0, "kernel": 0.0, "dense": 0, "replayed": 0}
+            t0 = time.perf_counter()
+            n = g.run()
+            run_s = time.perf_counter() - t0
+            kind = g.last_scan_kind()
+            p, s = collect(g, u, length, bw, clock, nondir=True)
+            if i >= warmup:
+                rows.append((run_s * 1e3, clock["profile"] * 1e3, clock["kernel"], clock))
+        h = hashlib.sha256()
+        h.update(p.tobytes())
+        h.update(s.tobytes())
+        tot = [a + b for a, b, _, _ in rows]
+        ker = [k for _, _, k, _ in rows]
+        clock = rows[-1][3]
+        med = lambda v: round(statistics.median(v), 3)
+        return {"contig": name, "bp": length, "bw": bw, "nondir": True, "wide_nd_full": full, "scan_kind": kind,
+                "lib": os.path.basename(capi.LIB_PATH), "tags": int(tags), "candidates": int(n),
+                "warmup": warmup, "reps": reps,
+                "run_ms": med([a for a, _, _, _ in rows]), "profile_ms": med([b for _, b, _, _ in rows]),
+                "total_ms": med(tot), "total_ms_min": round(min(tot), 3), "total_ms_max": round(max(tot), 3),
+                "kernel_ms": med(ker), "kernel_ms_min": round(min(ker), 3), "kernel_ms_max": round(max(ker), 3),
+                "dense_positions": clock["dense"], "replayed_entries": clock["replayed"],
+                "kernel_positions_per_s": (round(clock["dense"] / (statistics.median(ker) * 1e-3))
+                                           if min(ker) > 0 else None),
+                "nonzero": int(p.size), "sha256": h.hexdigest()}
+
+
 def check(a_path, b_path):
     """same profiles, and b faster than a, at every bandwidth"""
     def rows(p):
@@ -122,6 +176,8 @@ def main():
     ap.add_argument("--contig", default="chr21")
     ap.add_argument("--bw", type=int, nargs="+", default=[600, 2000])
     ap.add_argument("--reps", type=int, default=1)
+    ap.add_argument("--nondir", action="store_true", help="one nondirectional unit (see above)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed passes (--nondir)")
     ap.add_argument("--out")
     ap.add_argument("--check", nargs=2, metavar=("A", "B"))
     a = ap.parse_args()
@@ -134,7 +190,8 @@ def main():
     length = int(rows[ci][1])
     out = open(a.out, "w") if a.out else None
     for bw in a.bw:
-        line = json.dumps(measure(capi, a.contig, ci, length, bw, a.reps))
+        line = json.dumps(measure_nondir(capi, a.contig, ci, length, bw, a.reps, a.warmup) if a.nondir
+                          else measure(capi, a.contig, ci, length, bw, a.reps))
         print(line, flush=True)
         if out:
             out.write(line + "\n")

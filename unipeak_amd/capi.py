@@ -71,7 +71,7 @@ EXPORTS = [
     "up_reset_units", "up_run", "up_get_regions", "up_regions_view", "up_shift_scan", "up_shift_best",
     "up_timings", "up_scan_density", "up_unit_profile", "up_hbm_copy_gbps", "up_set_record_target",
     "up_host_register", "up_unit_profile_range", "up_run_async", "up_run_wait", "up_set_timing",
-    "up_set_profile_capture", "up_unit_replay_profile",
+    "up_set_profile_capture", "up_unit_replay_profile", "up_set_wide_nd_full",
     "up_set_index_policy", "up_invalidate_index", "up_index_state", "up_last_stats_kind", "up_last_exact_kind",
     "up_last_scan_kind",
     "up_tir_open", "up_tir_close", "up_tir_set_stream", "up_tir_query", "up_tir_timings",
@@ -138,6 +138,7 @@ def load_library(path=LIB_PATH):
         "up_host_register": (c.c_int, [vp, vp, c.c_uint64]),
         "up_unit_profile_range": (c.c_int, [vp, c.c_uint32, c.c_uint64, c.c_uint32, vp, vp]),
         "up_set_profile_capture": (c.c_int, [vp, c.c_int]),
+        "up_set_wide_nd_full": (c.c_int, [vp, c.c_int]),
         "up_unit_replay_profile": (c.c_int, [vp, c.c_uint32, u32p, c.POINTER(c.c_uint64), vp, vp, vp,
                                              c.c_uint64]),
         "up_tir_open": (c.c_int, [c.c_int, c.POINTER(vp)]),
@@ -152,6 +153,8 @@ def load_library(path=LIB_PATH):
         "up_cm_timings": (c.c_int, [vp, vp, c.c_int]),
     }
     for name, (res, args) in sig.items():
+        if os.environ.get("UNIPEAK_LIB") and not hasattr(L, name):
+            continue  # an A/B library of an older commit: calling what it lacks still raises
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -405,6 +408,11 @@ class Lib:
 
     def set_profile_capture(self, on):
         _ck(self.L.up_set_profile_capture(self.ctx, int(bool(on))))
+
+    def set_wide_nd_full(self, on):
+        """nondirectional units at bw 512..32767: K1w with the -w capture on, the dense
+        profile and run_async() as well (up_set_wide_nd_full; off by default)"""
+        _ck(self.L.up_set_wide_nd_full(self.ctx, int(bool(on))))
 
     def replay_profile(self, unit):
         """(resync, event[], pos[], score[]) of a replayed unit (up_unit_replay_profile)"""

@@ -208,6 +208,7 @@ struct up_ctx {
     bool k1b_one = true;             // pipelined K1b for one directional sample (UNIPEAK_K1B_ONE=0: off)
     bool k3_one = true;              // batched K3 for one directional sample (UNIPEAK_K3_ONE=0: off)
     bool wide_nd = true;             // K1w for nondirectional units (UNIPEAK_WIDE_ND=0: the replay)
+    bool wide_nd_full = false;       // those units' -w capture, dense profile and up_run_async (up_set_wide_nd_full)
     bool use_graphs = true;          // passes as hipGraphs (UNIPEAK_GRAPHS=0: plain launches)
     // streams of the passes: every K1a on one high-priority stream (stream
     // order serialises them; as resources free up the dispatcher serves it
@@ -1682,8 +1683,9 @@ static bool q11_whole_replay() {
 // K1w (wide.hip) for kernels wider than K1's halo: a threshold > 0 (directional
 // units with the -w capture on as well: head units hand their
 // retirements over from the K0 head replay, wide_profile_kernel gives the
-// dense rest; nondirectional units only with the capture off, and only inside
-// the blocking up_run -- wide_nd_mode), and a window of at most 65,535 cells
+// dense rest; nondirectional units by default only with the capture off, and
+// only inside the blocking up_run -- wide_nd_mode; up_set_wide_nd_full lifts
+// both), and a window of at most 65,535 cells
 // (bw <= kMaxWideBw): the reference counts
 // the cells add() retires in a UShort (misc/peakcall.cpp:172-177), so from
 // bw 32,768 on a gap of 2bw + 1 or more retires (gap mod 65,536) cells, the
@@ -1697,12 +1699,14 @@ static bool wide_mode(const up_ctx *c) {
         return !(e && *e == '0');
     }();
     return on && c->p.bw > kMaxBw && c->p.bw <= kMaxWideBw && kTB == 2 && c->p.region_thr > 0 &&
-           (!c->p.nondir || (c->wide_nd && !c->prof_capture));
+           (!c->p.nondir || (c->wide_nd && (!c->prof_capture || c->wide_nd_full)));
 }
 
-// K1w over both strands: its passes run only inside the blocking up_run
-// (run_wide_nd, as K1q's inside run_q11); up_run_async and the dense profile
-// of these units stay refused
+// K1w over both strands: by default its passes run only inside the blocking
+// up_run (run_wide_nd, as K1q's inside run_q11) and up_run_async and the
+// dense profile of these units stay refused; with up_set_wide_nd_full on,
+// nothing is (the pass state is per slot: d_wcorr and d_wslab, the
+// correlation kernel on the pass stream, no captured graph behind K1w)
 static bool wide_nd_mode(const up_ctx *c) { return c->p.nondir && wide_mode(c); }
 
 static bool replay_mode(const up_ctx *c) {
@@ -1724,7 +1728,7 @@ static int check_runnable(up_ctx *c, bool profile = false) {
     if (replay_mode(c)) return UP_E_UNSUPPORTED;
     // (the dense profile's window is K1's, or wide_profile_kernel's where K1w runs)
     if (profile && c->p.bw > kMaxBw && !wide_mode(c)) return UP_E_UNSUPPORTED;
-    if (wide_nd_mode(c) && (profile || !c->wide_nd_run)) return UP_E_UNSUPPORTED;
+    if (wide_nd_mode(c) && !c->wide_nd_full && (profile || !c->wide_nd_run)) return UP_E_UNSUPPORTED;
     return q11_mode(c) && !c->q11_run && !profile ? UP_E_UNSUPPORTED : UP_OK;
 }
 
@@ -3253,6 +3257,7 @@ int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t cou
     if (r) return r;
     if (busy(c)) return UP_E_STATE;  // a pass in flight reads this state
     if (unit >= c->units.size() || !out_f || first < 1 || count == 0) return UP_E_ARG;
+    if (!out_r && wide_nd_mode(c)) return UP_E_ARG;  // both strands' scores are the answer
     HIPCHK(hipSetDevice(c->dev));
     if ((r = sync_units(c))) return r;
     const Unit &u = c->units[unit];
@@ -3274,9 +3279,13 @@ int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t cou
         const dim3 grid((unsigned)std::min<uint64_t>(nstretch, 1u << 16));
         const size_t lds = prof_lds_bytes(c->p.bw);
         const int pm = pool_mode(c);
-        if (pm == 0) hipLaunchKernelGGL(wide_profile_kernel<0>, grid, dim3(64), lds, c->stream, P, cap);
-        else if (pm == 1) hipLaunchKernelGGL(wide_profile_kernel<1>, grid, dim3(64), lds, c->stream, P, cap);
-        else hipLaunchKernelGGL(wide_profile_kernel<2>, grid, dim3(64), lds, c->stream, P, cap);
+        if (c->p.nondir) {  // f and r, each its own ascending sum (up_set_wide_nd_full: check_runnable)
+            if (pm == 0) hipLaunchKernelGGL((wide_profile_kernel<0, true>), grid, dim3(64), lds, c->stream, P, cap);
+            else if (pm == 1) hipLaunchKernelGGL((wide_profile_kernel<1, true>), grid, dim3(64), lds, c->stream, P, cap);
+            else hipLaunchKernelGGL((wide_profile_kernel<2, true>), grid, dim3(64), lds, c->stream, P, cap);
+        } else if (pm == 0) hipLaunchKernelGGL((wide_profile_kernel<0, false>), grid, dim3(64), lds, c->stream, P, cap);
+        else if (pm == 1) hipLaunchKernelGGL((wide_profile_kernel<1, false>), grid, dim3(64), lds, c->stream, P, cap);
+        else hipLaunchKernelGGL((wide_profile_kernel<2, false>), grid, dim3(64), lds, c->stream, P, cap);
     } else {
         const uint32_t s0 = u.strip0 + (uint32_t)((first - 1) / kStrip);
         const uint32_t s1 = u.strip0 + (uint32_t)((first + count - 2) / kStrip) + 1;
@@ -3335,6 +3344,13 @@ int up_set_profile_capture(up_ctx *c, int on) {
     if (!c) return UP_E_ARG;
     if (busy(c)) return UP_E_STATE;
     c->prof_capture = on != 0;
+    return UP_OK;
+}
+
+int up_set_wide_nd_full(up_ctx *c, int on) {
+    if (!c) return UP_E_ARG;
+    if (busy(c)) return UP_E_STATE;
+    c->wide_nd_full = on != 0;
     return UP_OK;
 }
 

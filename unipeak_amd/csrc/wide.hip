@@ -28,7 +28,7 @@
 //
 // wide_stretch_scores (below): the dense FP64 scores of one strand over a
 // stretch of 64 words, the same ascending sums; its users are
-//  * wide_profile_kernel: the dense profile of a directional unit
+//  * wide_profile_kernel: the dense profile of a unit, one strand or both
 //    (up_unit_profile*, -w);
 //  * wide_corr_kernel: strandCorr(0) of every region of a nondirectional
 //    pass, between K2 and K3 (K3's own KDE spans NH <= 8 window words);
@@ -336,10 +336,18 @@ __device__ __forceinline__ void wide_stretch_scores(const ScanParams &P, const U
 
 // ---- the dense profile of a wide kernel (up_unit_profile*, bin/regions -w) ----
 // FP64 scores of positions [prof_first, prof_first + prof_len) of unit
-// prof_unit into the pre-zeroed prof_f (directional units only: prof_r stays
+// prof_unit into the pre-zeroed prof_f (a directional unit: prof_r stays
 // zero), each the ascending sum K1w forms.  One wave owns a stretch of
 // kProfWords words.  Positions above len + bw are never written.
-template <int POOL>
+// NONDIR: forwardScore into prof_f and reverseScore into prof_r, separate
+// ascending sums (the host adds them).  The screen is the unit's pooled plane,
+// which holds both strands' tags -- a word is live if either strand has a tag
+// in its union window -- and each strand takes its own gather and walk, one
+// after the other through the same hit list (the LDS stays the directional
+// kernel's), so one strand of a stretch may overflow the list and fall back to
+// wide_word_score while the other does not; a live word without a hit on a
+// strand stores the +0.0 its sum starts from.
+template <int POOL, bool NONDIR>
 __global__ void __launch_bounds__(64) wide_profile_kernel(ScanParams P, uint32_t cap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char prof_lds[];
     double *hcnt = (double *)prof_lds;
@@ -354,7 +362,7 @@ __global__ void __launch_bounds__(64) wide_profile_kernel(ScanParams P, uint32_t
     if (last < P.prof_first) return;
     const int64_t w_first = (P.prof_first - 1) >> 6, w_last = (last - 1) >> 6;  // words of 64 positions
     const int64_t nstretch = (w_last - w_first) / kProfWords + 1;
-    gu8 *pl = POOL == 0 ? plane_u8(U, S, 0, P.nc[0]) : pooled_u8(U, S);
+    gu8 *pl = (POOL == 0 && !NONDIR) ? plane_u8(U, S, 0, P.nc[0]) : pooled_u8(U, S);
     const int64_t nchunk_track = (int64_t)(U.stride / 4);
     for (int64_t s = blockIdx.x; s < nstretch; s += gridDim.x) {
         const int64_t w0 = w_first + s * kProfWords;
@@ -367,6 +375,15 @@ __global__ void __launch_bounds__(64) wide_profile_kernel(ScanParams P, uint32_t
                                              const int64_t q = x - P.prof_first;
                                              if (q >= 0 && q < (int64_t)P.prof_len && x <= dom_end) P.prof_f[q] = f;
                                          });
+        if constexpr (NONDIR) {
+            __syncthreads();  // the forward walk has read the list the reverse gather refills
+            wide_stretch_scores<POOL, false>(P, U, S, 1, bw, x_lo, nw, W, pre, cap, hcnt, hpos, lane,
+                                             [&](int64_t x, double r) {
+                                                 const int64_t q = x - P.prof_first;
+                                                 if (q >= 0 && q < (int64_t)P.prof_len && x <= dom_end)
+                                                     P.prof_r[q] = r;
+                                             });
+        }
     }
 }
 

@@ -413,6 +413,8 @@ void run_units(const EngineParams &ep, PassResult &out) {
         p.n_coeffs = (uint32_t)ep.coeffs.size();
         if ((rc = up_set_params(job.ctx, &p))) return fail(rc, "up_set_params");
         if (ep.profile && (rc = up_set_profile_capture(job.ctx, 1))) return fail(rc, "up_set_profile_capture");
+        // (-D above bw 511: K1w and the profile kernel with the capture on, not the whole-buffer replay)
+        if ((rc = up_set_wide_nd_full(job.ctx, 1))) return fail(rc, "up_set_wide_nd_full");
         std::vector<uint32_t> tp, tc;
         for (uint32_t gi : job.units) {
             const UnitBuild &u = out.units[gi];
