@@ -317,7 +317,9 @@ int up_scan_density(up_ctx *ctx, uint32_t *bytes_per_1024);
  * segment, [2]=K3 stats (with wide_corr_kernel, the strand correlation of a
  * nondirectional K1w pass, which runs just before K3), [3]=whole up_run wall, [4]=K1 launches; with n > 5
  * also [5]=the dense-profile kernel of the last up_unit_profile* call (HIP
- * events around it) */
+ * events around it); with n > 6 also [6]=K0 and [7]=the placement kernels of
+ * the last pass that placed its head units itself (up_set_head_place) at
+ * timing level 2, else 0 */
 /* achievable HBM rate: a float4 streaming copy kernel of `bytes` (a multiple
  * of 16; best of reps),
  * GB/s counting read + write (the bench's copy-rate reference) */
@@ -371,6 +373,33 @@ int up_unit_profile_range(up_ctx *ctx, uint32_t unit, uint64_t first, uint32_t c
  * and the refusals as well.  The records and the -w profile do not depend on
  * it; bin/regions sets it.  Making 1 the default is a later change. */
 int up_set_wide_nd_full(up_ctx *ctx, int on);
+/* Head units (quirk Q1) replayed and merged on the device, inside the pass.
+ * 0 (default): after a pass with head units up_run / up_run_wait run K0 on
+ *    the context stream, copy its records and the pass's K1-K3 records to the
+ *    host and merge them there, in the caller's thread (with a device record
+ *    target the merged list is copied up again): such passes do not overlap.
+ * 1: the pass runs K0 on its own stream into areas of its slot, K3 writes to
+ *    a device stage, and two kernels place both lists where the pass delivers
+ *    (the pinned host records or the record target, its header included) --
+ *    all stream-ordered before the pass's completion, no host round trip.
+ *    Scope: a threshold > 0, K1 and K1w passes, any units and samples, the -w
+ *    capture off.  With the capture on (its entries are gathered on the host),
+ *    at a threshold <= 0 and in the whole-context replay nothing changes; a
+ *    pass without head units launches nothing new.  When K0 runs out of an
+ *    in-pass capacity (an open region longer than its area, its record area
+ *    or its score slab) that pass is finished as with 0 -- which grows the
+ *    capacities for the passes after it.
+ * The initial value is 1 when UNIPEAK_HEAD_PLACE=1 is set at up_open.
+ * UP_E_STATE while a pass is in flight.  The records, up_shift_scan /
+ * up_shift_best and up_unit_replay_profile's resync do not depend on it;
+ * bin/regions and bin/strand_shift set it. */
+int up_set_head_place(up_ctx *ctx, int on);
+/* what the pass completed last did with its head units: 0 merged on the host,
+ * 1 replayed and placed inside the pass; -1 when no pass has completed, it
+ * had no head unit, or it took a whole-context path (K1q at a threshold <= 0,
+ * the replay of every unit).  For tests and A/B runs: the records do not
+ * depend on it. */
+int up_last_head_kind(up_ctx *ctx);
 
 /* ---- tags_in_regions (src/tags_in_regions.cpp:131-199) on the GPU ---------
  * A stream is one sample's alignment records in the order the reference's

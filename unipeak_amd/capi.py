@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UNIPEAK_LIB") or os.path.join(_HERE, "lib", "libunipeak_hip.so")
 
 UP_OK = 0
+UP_E_NOMEM, UP_E_STATE = -3, -4  # (include/unipeak_hip.h)
 MAX_IN_FLIGHT = 5  # UP_MAX_IN_FLIGHT (include/unipeak_hip.h)
 
 
@@ -73,7 +74,7 @@ EXPORTS = [
     "up_host_register", "up_unit_profile_range", "up_run_async", "up_run_wait", "up_set_timing",
     "up_set_profile_capture", "up_unit_replay_profile", "up_set_wide_nd_full",
     "up_set_index_policy", "up_invalidate_index", "up_index_state", "up_last_stats_kind", "up_last_exact_kind",
-    "up_last_scan_kind",
+    "up_last_scan_kind", "up_set_head_place", "up_last_head_kind",
     "up_tir_open", "up_tir_close", "up_tir_set_stream", "up_tir_query", "up_tir_timings",
     "up_cm_open", "up_cm_close", "up_cm_add", "up_cm_collect", "up_cm_timings",
 ]
@@ -139,6 +140,8 @@ def load_library(path=LIB_PATH):
         "up_unit_profile_range": (c.c_int, [vp, c.c_uint32, c.c_uint64, c.c_uint32, vp, vp]),
         "up_set_profile_capture": (c.c_int, [vp, c.c_int]),
         "up_set_wide_nd_full": (c.c_int, [vp, c.c_int]),
+        "up_set_head_place": (c.c_int, [vp, c.c_int]),
+        "up_last_head_kind": (c.c_int, [vp]),
         "up_unit_replay_profile": (c.c_int, [vp, c.c_uint32, u32p, c.POINTER(c.c_uint64), vp, vp, vp,
                                              c.c_uint64]),
         "up_tir_open": (c.c_int, [c.c_int, c.POINTER(vp)]),
@@ -413,6 +416,26 @@ class Lib:
         """nondirectional units at bw 512..32767: K1w with the -w capture on, the dense
         profile and run_async() as well (up_set_wide_nd_full; off by default)"""
         _ck(self.L.up_set_wide_nd_full(self.ctx, int(bool(on))))
+
+    def set_head_place(self, on):
+        """head units (quirk Q1) replayed and merged on the device inside the pass
+        (up_set_head_place; off by default, UNIPEAK_HEAD_PLACE=1 at open turns it on)"""
+        _ck(self.L.up_set_head_place(self.ctx, int(bool(on))))
+
+    def last_head_kind(self):
+        """head units of the pass completed last: 0 merged on the host, 1 replayed and
+        placed inside the pass, -1 none / a whole-context path (up_last_head_kind)"""
+        return int(self.L.up_last_head_kind(self.ctx))
+
+    def unit_resync(self, unit):
+        """the unit's resync position after the last pass: 0 not replayed, X replayed up
+        to X, 0xFFFFFFFF to its end (up_unit_replay_profile, with or without the capture)"""
+        rs, n = ctypes.c_uint32(), ctypes.c_uint64()
+        rc = self.L.up_unit_replay_profile(self.ctx, unit, ctypes.byref(rs), ctypes.byref(n), None, None,
+                                           None, 0)
+        if rc not in (UP_OK, UP_E_STATE) or (rc == UP_E_STATE and rs.value == 0):
+            _ck(rc)
+        return rs.value
 
     def replay_profile(self, unit):
         """(resync, event[], pos[], score[]) of a replayed unit (up_unit_replay_profile)"""

@@ -24,6 +24,7 @@
 #include "exact1.hip"   // (its LDS size)
 #include "emulate.hip"
 #include "q11place.hip"
+#include "headplace.hip"
 #include "wide.hip"
 
 namespace upk {
@@ -294,7 +295,21 @@ struct up_ctx {
         DevBuf<uint64_t> d_spk;          // K1 per-strip partial peaks (ScanParams::spk)
         DevBuf<double> d_corr;           // K3 (f, r) slabs for the strand correlation (-D -y)
         DevBuf<double> d_wcorr, d_wslab; // wide_corr_kernel: strandCorr(0) per region, its per-wave slabs
+        // head units placed inside the pass (headplace.hip): K3's stage, K0's
+        // outputs (records, exptSums, ranks, score offsets and slab; counters:
+        // records, error word, scores used; per unit: resync, records), the
+        // placement and the final list's columns for up_shift_scan
+        DevBuf<up_region> d_hp_stage, d_k0_out;
+        DevBuf<uint32_t> d_hp_stage_cnt, d_k0_counts, d_k0_rank, d_k0_ctr, d_k0_units;
+        DevBuf<uint64_t> d_k0_score_off, d_hp_soff;
+        DevBuf<double> d_k0_scores;
+        DevBuf<HeadPlace> d_hp_tab;
+        DevBuf<uint32_t> d_hp_st, d_hp_en, d_hp_un;
         void release() {
+            d_hp_stage.release(); d_k0_out.release(); d_hp_stage_cnt.release(); d_k0_counts.release();
+            d_k0_rank.release(); d_k0_ctr.release(); d_k0_units.release(); d_k0_score_off.release();
+            d_hp_soff.release(); d_k0_scores.release(); d_hp_tab.release(); d_hp_st.release();
+            d_hp_en.release(); d_hp_un.release();
             d_info.release(); d_rec.release(); d_ovf_count.release(); d_ovf_rec.release(); d_head.release();
             d_cnt.release(); d_nreg.release(); d_bsum.release(); d_starts.release(); d_ends.release();
             d_runit.release(); d_peak_pos.release(); d_xlist.release(); d_xcount.release();
@@ -313,6 +328,11 @@ struct up_ctx {
         uint32_t req_ovf_cap = 0;    // grows them, the launcher thread only reads these
         int req_tl = 0;
         bool req_q11 = false;
+        // the pass replays and places its head units itself (up_set_head_place),
+        // with these K0 capacities (emu_reg_cap, emu_out_cap, emu_scores_cap)
+        bool req_head_place = false, head_place = false;
+        uint32_t req_emu_reg_cap = 0, req_emu_out_cap = 0, k0_out_cap = 0;
+        uint64_t req_emu_scores_cap = 0;
         bool req_q11_place = false;  // the pass places its K1q records (q11_place)        // K1q instead of K1a/K1x/K1b (threshold <= 0, run_q11)
         bool lpending = false;       // queued for / being launched by the launcher thread
         int lrc = 0;                 // its launch result
@@ -324,6 +344,7 @@ struct up_ctx {
         int scan_kind = -1;          // the scan this pass launches: 0 K1, 1 K1w, 2 K1q (up_last_scan_kind)
         std::chrono::steady_clock::time_point t0;
         hipEvent_t ev[5] = {};       // K1a begin, K1a end, K1b end, K2 end, K3 end
+        hipEvent_t hev[3] = {};      // a placed pass at timing level 2: K0 begin, K0 end, placement end
         hipEvent_t done = nullptr;
     } pass[kSlots];
     uint64_t seq_launched = 0, seq_done = 0;
@@ -375,6 +396,23 @@ struct up_ctx {
     DevBuf<uint32_t> d_seg_n, d_gbeg, d_gend;
     uint32_t emu_out_cap = 1u << 16;     // K0: region records
     bool host_regions = false;  // merged list lives on the host
+    // head units replayed and merged inside the pass (up_set_head_place,
+    // headplace.hip): the mode; what the pass completed last did; the current
+    // records are such a list; the layout-time tables (head flags, chain
+    // groups: functions of the tracks, bw and the pooling) on the device and
+    // what the host keeps of them; K0 launches of successive passes share the
+    // context's scratch, ordered by k0_done; per slot the resync positions
+    bool head_place = false;
+    int last_head_kind = -1;
+    double head_ms[2] = {0, 0};  // the last placed pass timed at level 2: K0, placement (up_timings [6], [7])
+    bool head_placed = false;
+    bool head_tab_valid = false, hp_any_head = false;
+    uint32_t hp_ngroups = 0;
+    DevBuf<uint32_t> d_hp_head, d_hp_gunits, d_hp_goff;
+    DevBuf<int32_t> d_hp_ubuf;
+    hipEvent_t k0_done = nullptr;
+    bool k0_done_set = false;
+    HostBuf<uint32_t> hp_resync[kSlots];
     // threshold <= 0 through K1q (run_q11): the blocking pass in progress,
     // and per host record the unit whose tracks hold its positions (a region
     // closed in the buffer's next unit keeps the previous unit's positions)
@@ -496,6 +534,7 @@ int up_index_state(up_ctx *c, int *on, uint64_t *builds) {
 int up_last_stats_kind(up_ctx *c) { return c ? c->last_k3_kind : -1; }
 int up_last_exact_kind(up_ctx *c) { return c ? c->last_k1b_kind : -1; }
 int up_last_scan_kind(up_ctx *c) { return c ? c->last_scan_kind : -1; }
+int up_last_head_kind(up_ctx *c) { return c ? c->last_head_kind : -1; }
 
 const char *up_strerror(int code) {
     switch (code) {
@@ -554,6 +593,7 @@ int up_open(int hip_device, up_ctx **out) {
     if (const char *e = getenv("UNIPEAK_K1B_BLOCKS")) c->k1b_blocks = std::max(0, atoi(e));
     if (const char *e = getenv("UNIPEAK_CHAINS")) c->n_chain = std::min(4, std::max(1, atoi(e)));
     if (const char *e = getenv("UNIPEAK_LAUNCHER")) c->use_launcher = e[0] != '0';
+    if (const char *e = getenv("UNIPEAK_HEAD_PLACE")) c->head_place = atoi(e) != 0;
     {
         int least = 0, greatest = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -574,10 +614,12 @@ int up_open(int hip_device, up_ctx **out) {
     for (auto &e : c->ev) HIPCHK(hipEventCreate(&e));
     for (auto &ps : c->pass) {
         for (auto &e : ps.ev) HIPCHK(hipEventCreate(&e));
+        for (auto &e : ps.hev) HIPCHK(hipEventCreate(&e));
         HIPCHK(hipEventCreateWithFlags(&ps.done, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&ps.k1a_end, hipEventDisableTiming));
     }
     HIPCHK(hipEventCreateWithFlags(&c->host_work, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->k0_done, hipEventDisableTiming));
     for (auto &e : c->scat_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     *out = c;
     return UP_OK;
@@ -629,6 +671,7 @@ void up_close(up_ctx *c) {
     for (int k = 0; k < kSlots; ++k) {
         c->hp_regions[k].release(); c->hp_counts[k].release(); c->hp_status[k].release(); c->hp_head[k].release();
         for (auto &e : c->pass[k].ev) (void)hipEventDestroy(e);
+        for (auto &e : c->pass[k].hev) (void)hipEventDestroy(e);
         (void)hipEventDestroy(c->pass[k].done);
         (void)hipEventDestroy(c->pass[k].k1a_end);
         for (auto &g : c->pass[k].graphs) (void)hipGraphExecDestroy(g.second);
@@ -638,6 +681,9 @@ void up_close(up_ctx *c) {
     for (auto st : c->chain)
         if (st) (void)hipStreamDestroy(st);
     (void)hipEventDestroy(c->host_work);
+    (void)hipEventDestroy(c->k0_done);
+    c->d_hp_head.release(); c->d_hp_gunits.release(); c->d_hp_goff.release(); c->d_hp_ubuf.release();
+    for (auto &h : c->hp_resync) h.release();
     for (auto &e : c->scat_ev) (void)hipEventSynchronize(e);
     c->hp_scat[0].release(); c->hp_scat[1].release();
     for (auto &e : c->scat_ev) (void)hipEventDestroy(e);
@@ -677,6 +723,7 @@ int up_set_params(up_ctx *c, const up_params *p) {
     c->p.is_control = nullptr;
     c->p.coeffs = nullptr;
     if (!same) {
+        c->head_tab_valid = false;  // (the head flags follow the pooling)
         c->ctl = ctl;
         c->nc = nc;
         c->coef = coef;
@@ -1197,6 +1244,7 @@ static int regrow_unit(up_ctx *c, Unit &u) {
 static int sync_layout(up_ctx *c) {
     if (!c->units_dirty && c->bw_layout == c->p.bw) return UP_OK;
     c->aligned_valid = false;
+    c->head_tab_valid = false;
     for (Unit &u : c->units)
         if ((uint32_t)c->p.bw > u.pad_bw) {
             if (int r = regrow_unit(c, u)) return r;
@@ -2063,6 +2111,7 @@ static int replay_head_hits(up_ctx *c, int slot) {
     c->h_resync.assign(nu, 0);  // no unit replayed (yet)
     c->h_pf_off.assign(nu + 1, 0);
     if (!any) return UP_OK;
+    c->last_head_kind = 0;  // merged on the host (up_last_head_kind)
     // the head flags are a function of the (unchanged) tracks, so d_head of
     // a later pass still describes this one
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2186,6 +2235,227 @@ static int q11_place(up_ctx *c, int slot, hipStream_t st, const Q11Edit *d_edit,
     return UP_OK;
 }
 
+// a pass of this context may replay and place its head units itself
+// (headplace.hip): the mode is on, a threshold > 0, the -w capture off (its
+// entries are gathered on the host, emulate_units)
+static bool head_place_mode(const up_ctx *c) {
+    return c->head_place && c->p.region_thr > 0 && !c->prof_capture && !c->q11_run;
+}
+
+// the layout-time tables of head_place_mode: head flags, "aligned" flags and
+// K0's chain groups (emulate_units) -- functions of the tracks, bw and the
+// pooling, computed once per layout (sync_layout and up_set_params drop
+// them; neither runs while a pass is in flight), so the host knows before it
+// launches a pass whether that pass has head units
+static int sync_head_tables(up_ctx *c) {
+    if (c->head_tab_valid) return UP_OK;
+    const uint32_t nu = (uint32_t)c->units.size();
+    const int S = c->p.n_samples;
+    c->hp_any_head = false;
+    c->hp_ngroups = 0;
+    if (nu == 0) {
+        c->head_tab_valid = true;
+        return UP_OK;
+    }
+    HIPCHK(c->d_hp_head.ensure(nu));
+    std::vector<uint32_t> head(nu, 0), aligned(nu, 0);
+    if (pool_mode(c) == 2)
+        hipLaunchKernelGGL(head_flags_kernel<2>, dim3(nu), dim3(256), 0, c->stream, c->d_units.p, S,
+                           (int)c->nc.size(), c->d_nc.p, c->d_coef.p, (int)c->p.bw, c->d_hp_head.p);
+    else
+        hipLaunchKernelGGL(head_flags_kernel<1>, dim3(nu), dim3(256), 0, c->stream, c->d_units.p, S,
+                           (int)c->nc.size(), c->d_nc.p, c->d_coef.p, (int)c->p.bw, c->d_hp_head.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(head.data(), c->d_hp_head.p, nu * 4, hipMemcpyDeviceToHost, c->stream));
+    if (c->aligned_valid && c->aligned_cache.size() == nu) {
+        aligned = c->aligned_cache;
+    } else {
+        HIPCHK(c->d_q11_head.ensure(nu));
+        HIPCHK(hipMemsetAsync(c->d_q11_head.p, 0, nu * sizeof(uint32_t), c->stream));
+        hipLaunchKernelGGL(unit_aligned_kernel, dim3(nu), dim3(256), 0, c->stream, c->d_units.p, S, (int)c->p.bw,
+                           c->d_q11_head.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(aligned.data(), c->d_q11_head.p, nu * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->aligned_cache = aligned;
+    c->aligned_valid = true;
+    for (uint32_t v : head) c->hp_any_head |= v != 0;
+    // chain groups: a new group after every unit with an add past bw
+    std::vector<uint32_t> gunits, goff{0};
+    std::vector<int32_t> ub(nu);
+    {
+        std::vector<std::vector<uint32_t>> groups;
+        int64_t open[2] = {-1, -1};
+        for (uint32_t u = 0; u < nu; ++u) {
+            const int b = c->units[u].buffer & 1;
+            ub[u] = c->units[u].buffer;
+            if (open[b] < 0) {
+                open[b] = (int64_t)groups.size();
+                groups.emplace_back();
+            }
+            groups[open[b]].push_back(u);
+            if (aligned[u]) open[b] = -1;
+        }
+        for (const auto &g : groups) {
+            gunits.insert(gunits.end(), g.begin(), g.end());
+            goff.push_back((uint32_t)gunits.size());
+        }
+    }
+    c->hp_ngroups = (uint32_t)goff.size() - 1;
+    HIPCHK(c->d_hp_gunits.ensure(gunits.size()));
+    HIPCHK(c->d_hp_goff.ensure(goff.size()));
+    HIPCHK(c->d_hp_ubuf.ensure(nu));
+    HIPCHK(hipMemcpy(c->d_hp_gunits.p, gunits.data(), gunits.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_hp_goff.p, goff.data(), goff.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_hp_ubuf.p, ub.data(), nu * sizeof(int32_t), hipMemcpyHostToDevice));
+    c->head_tab_valid = true;
+    return UP_OK;
+}
+
+// K0 of a placed pass on its stream: emulate_kernel over the head chains
+// into the slot's own output areas.  The working scratch (rings, open-region
+// areas) is the context's: the K0 launches of successive passes are ordered
+// by k0_done.  K0 reads only the tracks, so it is enqueued ahead of the
+// pass's wait for its K1a and runs beside it.
+static int launch_k0_in_pass(up_ctx *c, int slot) {
+    up_ctx::Pass &ps = c->pass[slot];
+    hipStream_t st = ps.stream;
+    const uint32_t nu = (uint32_t)c->units.size();
+    const int S = c->p.n_samples;
+    const uint32_t W = 2u * c->p.bw + 1;
+    const uint32_t reg_cap = ps.req_emu_reg_cap, out_cap = ps.req_emu_out_cap;
+    const uint32_t ngroups = c->hp_ngroups;
+    const size_t ring_bytes = (size_t)W * (2 * sizeof(double) + 1);
+    const bool ring_lds = ring_bytes + sizeof(EmuLds) <= 65536 - 64;
+    // workgroups (scratch slots) as emulate_units sizes them
+    const uint64_t slot_bytes = (uint64_t)W * S * 4 + (uint64_t)reg_cap * (8 + 8 + 4 + 4ull * S) +
+                                (ring_lds ? 0 : (uint64_t)W * 17);
+    const uint32_t nslots = (uint32_t)std::max<uint64_t>(
+        1, std::min<uint64_t>({(uint64_t)std::max(ngroups, 1u), 256u, (1ull << 30) / std::max<uint64_t>(slot_bytes, 1)}));
+    HIPCHK(c->d_ring_hits.ensure((uint64_t)nslots * W * S));
+    if (!ring_lds) {
+        HIPCHK(c->d_ring_f.ensure((uint64_t)nslots * W));
+        HIPCHK(c->d_ring_r.ensure((uint64_t)nslots * W));
+        HIPCHK(c->d_ring_has.ensure((uint64_t)nslots * W));
+    }
+    HIPCHK(c->d_reg_f.ensure((uint64_t)nslots * reg_cap));
+    HIPCHK(c->d_reg_r.ensure((uint64_t)nslots * reg_cap));
+    HIPCHK(c->d_reg_hit.ensure((uint64_t)nslots * reg_cap));
+    HIPCHK(c->d_reg_hits.ensure((uint64_t)nslots * reg_cap * S));
+    HIPCHK(ps.d_k0_out.ensure(out_cap));
+    HIPCHK(ps.d_k0_counts.ensure((size_t)out_cap * S));
+    HIPCHK(ps.d_k0_rank.ensure(out_cap));
+    HIPCHK(ps.d_k0_score_off.ensure(out_cap));
+    HIPCHK(ps.d_k0_scores.ensure(ps.req_emu_scores_cap));
+    HIPCHK(ps.d_k0_ctr.ensure(4));
+    HIPCHK(ps.d_k0_units.ensure(2 * (size_t)nu));
+    ps.k0_out_cap = out_cap;
+    if (c->k0_done_set) HIPCHK(hipStreamWaitEvent(st, c->k0_done, 0));
+    HIPCHK(hipMemsetAsync(ps.d_k0_ctr.p, 0, 4 * sizeof(uint32_t), st));
+    HIPCHK(hipMemsetAsync(ps.d_k0_units.p, 0, 2 * (size_t)nu * sizeof(uint32_t), st));
+    if (!ring_lds) {
+        HIPCHK(hipMemsetAsync(c->d_ring_f.p, 0, (uint64_t)nslots * W * sizeof(double), st));
+        HIPCHK(hipMemsetAsync(c->d_ring_r.p, 0, (uint64_t)nslots * W * sizeof(double), st));
+        HIPCHK(hipMemsetAsync(c->d_ring_has.p, 0, (uint64_t)nslots * W, st));
+    }
+    EmuParams E{};
+    E.units = c->d_units.p;
+    E.nunits = nu;
+    E.unit_buffer = c->d_hp_ubuf.p;
+    E.gunits = c->d_hp_gunits.p;
+    E.goff = c->d_hp_goff.p;
+    E.ngroups = ngroups;
+    E.unit_head = c->d_hp_head.p;
+    E.S = S;
+    E.nnc = (int32_t)c->nc.size();
+    E.nc = c->d_nc.p;
+    E.is_control = c->d_ctl.p;
+    E.coef = c->d_coef.p;
+    E.ncoef = (int32_t)c->coef.size();
+    E.kern = c->d_kern.p;
+    E.bw = c->p.bw;
+    E.nondir = c->p.nondir;
+    E.region_thr = c->p.region_thr;
+    E.kurt_thr = c->p.kurt_thr;
+    E.corr_thr = c->p.corr_thr;
+    E.hit_thr = c->p.hit_thr;
+    E.want_corr = c->p.want_corr || c->p.corr_thr > -1;
+    E.resync = ps.d_k0_units.p;
+    E.unit_n = ps.d_k0_units.p + nu;
+    E.out = ps.d_k0_out.p;
+    E.out_counts = ps.d_k0_counts.p;
+    E.out_rank = ps.d_k0_rank.p;
+    E.nout = ps.d_k0_ctr.p;
+    E.err = ps.d_k0_ctr.p + 1;
+    E.nscores = (unsigned long long *)(ps.d_k0_ctr.p + 2);
+    E.out_cap = out_cap;
+    E.ring_hits = c->d_ring_hits.p;
+    E.reg_f = c->d_reg_f.p;
+    E.reg_r = c->d_reg_r.p;
+    E.reg_hit = c->d_reg_hit.p;
+    E.reg_hits = c->d_reg_hits.p;
+    E.reg_cap = reg_cap;
+    E.ring_lds = ring_lds ? 1 : 0;
+    E.ring_f = c->d_ring_f.p;
+    E.ring_r = c->d_ring_r.p;
+    E.ring_has = c->d_ring_has.p;
+    E.out_scores = ps.d_k0_scores.p;
+    E.out_score_off = ps.d_k0_score_off.p;
+    E.scores_cap = ps.req_emu_scores_cap;
+    if (ps.req_tl >= 2) HIPCHK(hipEventRecord(ps.hev[0], st));
+    hipLaunchKernelGGL(emulate_kernel, dim3(nslots), dim3(64), ring_lds ? ring_bytes : 0, st, E);
+    HIPCHK(hipGetLastError());
+    if (ps.req_tl >= 2) HIPCHK(hipEventRecord(ps.hev[1], st));
+    HIPCHK(hipEventRecord(c->k0_done, st));
+    c->k0_done_set = true;
+    return UP_OK;
+}
+
+// the records' destination of a placed pass and its capacity
+static void head_dest(up_ctx *c, int slot, up_region *&out, uint32_t *&oc, uint64_t &dcap) {
+    up_ctx::Pass &ps = c->pass[slot];
+    if (ps.target) {
+        out = (up_region *)(ps.target + 8);
+        oc = (uint32_t *)(ps.target + 8 + ps.target_cap * sizeof(up_region));
+        dcap = std::min<uint64_t>(ps.cap, ps.target_cap);
+    } else {
+        out = c->hp_regions[slot].dev;
+        oc = c->hp_counts[slot].dev;
+        dcap = ps.cap;
+    }
+}
+
+// a placed pass behind K3: the per-unit placement and the copy of both
+// lists into the pass's destination (headplace.hip)
+static int head_place_launch(up_ctx *c, int slot, hipStream_t st) {
+    up_ctx::Pass &ps = c->pass[slot];
+    const uint32_t nu = (uint32_t)c->units.size();
+    up_region *out;
+    uint32_t *oc;
+    uint64_t dcap;
+    head_dest(c, slot, out, oc, dcap);
+    HeadK0 K{};
+    K.out = ps.d_k0_out.p;
+    K.counts = ps.d_k0_counts.p;
+    K.rank = ps.d_k0_rank.p;
+    K.score_off = ps.d_k0_score_off.p;
+    K.ctr = ps.d_k0_ctr.p;
+    K.resync = ps.d_k0_units.p;
+    K.unit_n = ps.d_k0_units.p + nu;
+    K.out_cap = ps.k0_out_cap;
+    hipLaunchKernelGGL(head_table_kernel, dim3(1), dim3(1024), 0, st, nu, ps.d_runit.p, ps.d_hp_stage.p,
+                       ps.d_nreg.p, K, ps.d_hp_tab.p, c->hp_resync[slot].dev, c->hp_status[slot].dev,
+                       (unsigned long long *)ps.target, dcap);
+    HIPCHK(hipGetLastError());
+    HeadLists Lst{ps.d_hp_st.p, ps.d_hp_en.p, ps.d_hp_un.p, ps.d_hp_soff.p};
+    const unsigned blocks = (unsigned)std::min<uint64_t>((ps.cap * 8 + 255) / 256 + 1, 4096);
+    hipLaunchKernelGGL(head_scatter_kernel, dim3(blocks), dim3(256), 0, st, ps.d_hp_stage.p, ps.d_hp_stage_cnt.p,
+                       ps.d_nreg.p, (int)c->p.n_samples, K, ps.d_hp_tab.p, nu, out, oc, dcap, Lst);
+    HIPCHK(hipGetLastError());
+    return UP_OK;
+}
+
 static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatParams &P, uint64_t cap,
                         uint32_t k1a_waves, uint32_t k1a_xcap, bool events) {
     up_ctx::Pass &ps = c->pass[slot];
@@ -2201,7 +2471,8 @@ static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatPar
         HIPCHK(hipGetLastError());
     }
     if (events) HIPCHK(hipEventRecord(ps.ev[2], ps.stream));
-    unsigned long long *thdr = (unsigned long long *)ps.target;
+    // (a placed pass's count is the merged one: head_table_kernel writes the header)
+    unsigned long long *thdr = ps.head_place ? nullptr : (unsigned long long *)ps.target;
     if (int r = launch_seg_count_head(c, slot)) return r;
     hipLaunchKernelGGL(seg_compact_kernel, dim3(nsb), dim3(kSegBlock), 0, ps.stream, c->d_units.p,
                        (uint32_t)c->units.size(), ps.d_info.p, ps.d_cnt.p, ps.d_bsum.p, ps.d_rec.p,
@@ -2235,6 +2506,10 @@ static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatPar
     if (ps.req_q11_place)
         if (int r = q11_place(c, slot, ps.stream, nullptr, true)) return r;
     if (events) HIPCHK(hipEventRecord(ps.ev[4], ps.stream));
+    if (ps.head_place) {  // (after K3's event: up_timings [2] stays K3's own time)
+        if (int r = head_place_launch(c, slot, ps.stream)) return r;
+        if (events) HIPCHK(hipEventRecord(ps.hev[2], ps.stream));
+    }
     return UP_OK;
 }
 
@@ -2259,7 +2534,7 @@ static int launch_pass(up_ctx *c, int slot) {
     HIPCHK(ps.d_cnt.ensure(ns));
     HIPCHK(ps.d_bsum.ensure(nsb));
     HIPCHK(ps.d_nreg.ensure(1));
-    HIPCHK(c->hp_status[slot].ensure(4));
+    HIPCHK(c->hp_status[slot].ensure(8));
     if (!ps.d_xcount.p || !ps.d_ovf_count.p) ps.counters_armed = false;
     HIPCHK(ps.d_xcount.ensure(2));  // front / back ends of the work list
     HIPCHK(ps.d_ovf_count.ensure(1));
@@ -2295,6 +2570,17 @@ static int launch_pass(up_ctx *c, int slot) {
     ps.target_cap = ps.req_target_cap;
     ps.cap = cap;
     ps.ovf_cap = ovf_cap;
+    ps.head_place = ps.req_head_place;
+    if (ps.head_place) {  // K3's stage, the placement, the final list's columns
+        HIPCHK(ps.d_hp_stage.ensure(cap + 1));
+        HIPCHK(ps.d_hp_stage_cnt.ensure((cap + 1) * S));
+        HIPCHK(ps.d_hp_tab.ensure(c->units.size()));
+        HIPCHK(ps.d_hp_st.ensure(cap + 1));
+        HIPCHK(ps.d_hp_en.ensure(cap + 1));
+        HIPCHK(ps.d_hp_un.ensure(cap + 1));
+        HIPCHK(ps.d_hp_soff.ensure(cap + 1));
+        HIPCHK(c->hp_resync[slot].ensure(c->units.size()));
+    }
     // the pass follows everything enqueued on the context stream (track
     // writes), and its K1a follows the K1a of the previous pass if that one
     // is in flight: one streaming K1a at a time, earlier passes' K1b/K2/K3
@@ -2308,11 +2594,14 @@ static int launch_pass(up_ctx *c, int slot) {
     if (hipStreamQuery(c->stream) != hipSuccess) {
         HIPCHK(hipEventRecord(c->host_work, c->stream));
         HIPCHK(hipStreamWaitEvent(s1, c->host_work, 0));
+        if (ps.head_place) HIPCHK(hipStreamWaitEvent(ps.stream, c->host_work, 0));  // (K0 reads the tracks)
     }
     if (!ps.counters_armed) {  // K2b re-arms them at the end of every pass
         HIPCHK(hipMemsetAsync(ps.d_ovf_count.p, 0, sizeof(uint32_t), s1));
         HIPCHK(hipMemsetAsync(ps.d_xcount.p, 0, 2 * sizeof(uint32_t), s1));
     }
+    if (ps.head_place)
+        if (int r = launch_k0_in_pass(c, slot)) return r;
     ScanParams SP = scan_params(c, ps, ovf_cap);
     // K1x..K3 as a captured graph only when the caller's thread launches:
     // capturing on the launcher thread while the caller waits on earlier
@@ -2350,6 +2639,11 @@ static int launch_pass(up_ctx *c, int slot) {
     } else {
         P.out = c->hp_regions[slot].dev;
         P.out_counts = c->hp_counts[slot].dev;
+    }
+    if (ps.head_place) {  // K3 -> the slot's stage; headplace.hip merges it with K0's records
+        P.cap = cap;
+        P.out = ps.d_hp_stage.p;
+        P.out_counts = ps.d_hp_stage_cnt.p;
     }
     ps.counters_armed = true;  // K2b re-arms them
     const int tl = ps.tl;
@@ -2424,6 +2718,24 @@ static int launch_pass(up_ctx *c, int slot) {
     key_add(key, ps.target);
     key_add(key, ps.d_cnt.p);
     key_add(key, ps.d_bsum.p);
+    key_add(key, ps.head_place);
+    if (ps.head_place) {  // head_place_launch's arguments (K3's stage is in P)
+        key_add(key, ps.d_k0_out.p);
+        key_add(key, ps.d_k0_counts.p);
+        key_add(key, ps.d_k0_rank.p);
+        key_add(key, ps.d_k0_score_off.p);
+        key_add(key, ps.d_k0_ctr.p);
+        key_add(key, ps.d_k0_units.p);
+        key_add(key, ps.k0_out_cap);
+        key_add(key, ps.d_hp_tab.p);
+        key_add(key, ps.d_hp_st.p);
+        key_add(key, ps.d_hp_en.p);
+        key_add(key, ps.d_hp_un.p);
+        key_add(key, ps.d_hp_soff.p);
+        key_add(key, c->hp_resync[slot].dev);
+        key_add(key, ps.target_cap);
+        key_add(key, cap);
+    }
     size_t gi = 0;
     while (gi < ps.graphs.size() && ps.graphs[gi].first != key) ++gi;
     if (gi == ps.graphs.size()) {
@@ -2522,6 +2834,14 @@ int up_run_async(up_ctx *c) {
     ps.req_last_nreg = c->last_nreg;
     ps.req_reg_cap = c->reg_cap;
     ps.req_ovf_cap = c->ovf_cap;
+    ps.req_head_place = false;
+    if (head_place_mode(c)) {  // the pass replays and places its head units itself, if it has any
+        if ((r = sync_head_tables(c))) return r;
+        ps.req_head_place = c->hp_any_head;
+        ps.req_emu_reg_cap = c->emu_reg_cap;
+        ps.req_emu_out_cap = c->emu_out_cap;
+        ps.req_emu_scores_cap = c->emu_scores_cap;
+    }
     if (c->use_launcher) {
         if (!c->launcher.joinable()) c->launcher = std::thread(launcher_main, c);
         {
@@ -2551,6 +2871,8 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     c->nreg = 0;
     c->host_regions = false;
     c->q11_placed = false;
+    c->head_placed = false;
+    c->last_head_kind = -1;
     c->cur_slot = slot;
     c->last_k3_kind = -1;
     c->last_k1b_kind = -1;
@@ -2573,7 +2895,7 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     }
     if (ps.lrc) return fail(ps.lrc);
     if (hipEventSynchronize(ps.done) != hipSuccess) return fail(UP_E_HIP);
-    uint64_t nreg = 0;
+    uint64_t nreg = 0, placed_total = 0;
     for (int attempt = 0;; ++attempt) {
         if (attempt == 3) return fail(UP_E_INTERNAL);
         const unsigned long long *st = c->hp_status[slot].p;
@@ -2584,6 +2906,14 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
         if (ovf > ps.ovf_cap) { c->ovf_cap = std::max<uint32_t>(c->ovf_cap, (uint32_t)(ovf + ovf / 2 + 64)); again = true; }
         if (nreg > ps.cap) { c->reg_cap = std::max<uint64_t>(c->reg_cap, nreg + nreg / 4 + 1024); again = true; }
         if (ps.target && nreg > ps.target_cap) return fail(UP_E_NOMEM);  // caller's buffer too small
+        if (ps.head_place && !again) {  // the merged count against the destination (headplace.hip)
+            placed_total = st[kHeadStTotal] ? st[kHeadStTotal] - 1 : 0;
+            if (ps.target && placed_total > ps.target_cap) return fail(UP_E_NOMEM);
+            if (placed_total > ps.cap) {
+                c->reg_cap = std::max<uint64_t>(c->reg_cap, placed_total + placed_total / 4 + 1024);
+                again = true;
+            }
+        }
 #if defined(UPK_DEBUG_COUNTS) || defined(UPK_DEBUG_TIMES)
         if (getenv("UNIPEAK_DEBUG_COUNTS")) {
             unsigned long long h[32];
@@ -2619,7 +2949,36 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     c->last_k1b_kind = ps.k1b_kind;
     c->last_scan_kind = ps.scan_kind;  // (head units' K0 chains aside)
     // (a K1q pass's head units take q11_finish's chains instead)
-    int r = ps.req_q11 ? UP_OK : replay_head_hits(c, slot);
+    int r = UP_OK;
+    if (ps.req_q11) {
+        // (nothing here: q11_finish's chains take its head units)
+    } else if (ps.head_place && !(c->hp_status[slot].p[kHeadStErr] & kHeadK0Bad)) {
+        // replayed and merged inside the pass: the slot holds the final list
+        const uint32_t nu = (uint32_t)c->units.size();
+        c->nreg = placed_total;
+        c->head_placed = true;
+        c->last_head_kind = 1;
+        c->h_resync.assign(c->hp_resync[slot].p, c->hp_resync[slot].p + nu);
+        c->head_ms[0] = c->head_ms[1] = 0;
+        if (ps.tl >= 2) {
+            float k0 = 0, pl = 0;
+            (void)hipEventElapsedTime(&k0, ps.hev[0], ps.hev[1]);
+            (void)hipEventElapsedTime(&pl, ps.ev[4], ps.hev[2]);
+            c->head_ms[0] = k0;
+            c->head_ms[1] = pl;
+        }
+        c->h_pf_off.assign(nu + 1, 0);
+    } else {
+        if (ps.head_place) {
+            // K0 ran out of one of its in-pass capacities: the placement left
+            // K3's records as they were, and the host path finishes this pass
+            // (it grows the capacities, which the next pass then takes); the
+            // K0 launches of later passes in flight share its scratch
+            launcher_drain(c);
+            if (hipDeviceSynchronize() != hipSuccess) return fail(UP_E_HIP);
+        }
+        r = replay_head_hits(c, slot);
+    }
     if (r) return fail(r);
     const int tl = ps.tl;
     float a = 0, b = 0, d = 0, x = 0;
@@ -2734,6 +3093,8 @@ static int run_replay(up_ctx *c, uint64_t *n_regions) {
     c->nreg = 0;
     c->host_regions = false;
     c->q11_placed = false;
+    c->head_placed = false;
+    c->last_head_kind = -1;
     c->last_k3_kind = -1;  // K0 computes the replay's statistics
     c->last_k1b_kind = -1;
     c->last_scan_kind = c->units.empty() ? -1 : 3;
@@ -3123,6 +3484,7 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
     up_ctx::Pass &ps = c->pass[c->cur_slot];  // the last completed pass's region lists
     std::vector<uint32_t> st(c->nreg), en(c->nreg);
     std::unordered_map<uint64_t, uint64_t> qrep;  // placed K1q list: its replayed records
+    std::vector<uint64_t> hsoff;                  // head_placed list: score offsets (kHeadNoScores: not replayed)
     if (c->q11_placed) {
         // K1q records: their stored positions left - 1 .. right - 1 of their
         // source unit, as q11_scatter_kernel wrote them
@@ -3137,6 +3499,22 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
         HIPCHK(hipMemcpy(ps.d_starts.p, c->d_q11_st.p, c->nreg * 4, hipMemcpyDeviceToDevice));
         HIPCHK(hipMemcpy(ps.d_ends.p, c->d_q11_en.p, c->nreg * 4, hipMemcpyDeviceToDevice));
         HIPCHK(hipMemcpy(ps.d_runit.p, c->d_q11_src.p, c->nreg * 4, hipMemcpyDeviceToDevice));
+    } else if (c->head_placed) {
+        // a list merged inside the pass: head_scatter_kernel left every final
+        // record's stored start, end and unit and, for a replayed one, the
+        // offset of its scores in the slot's slab
+        hsoff.resize(c->nreg);
+        if (c->nreg) {
+            HIPCHK(hipMemcpy(st.data(), ps.d_hp_st.p, c->nreg * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(en.data(), ps.d_hp_en.p, c->nreg * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hsoff.data(), ps.d_hp_soff.p, c->nreg * 8, hipMemcpyDeviceToHost));
+        }
+        HIPCHK(ps.d_starts.ensure(c->nreg + 1));
+        HIPCHK(ps.d_ends.ensure(c->nreg + 1));
+        HIPCHK(ps.d_runit.ensure(c->nreg + 1));
+        HIPCHK(hipMemcpy(ps.d_starts.p, ps.d_hp_st.p, c->nreg * 4, hipMemcpyDeviceToDevice));
+        HIPCHK(hipMemcpy(ps.d_ends.p, ps.d_hp_en.p, c->nreg * 4, hipMemcpyDeviceToDevice));
+        HIPCHK(hipMemcpy(ps.d_runit.p, ps.d_hp_un.p, c->nreg * 4, hipMemcpyDeviceToDevice));
     } else if (c->host_regions) {
         // replayed (Q1) regions carry state-machine scores the dense KDE
         // cannot reproduce; refuse rather than return something else
@@ -3172,7 +3550,8 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
         if (idx[j] >= c->nreg) return UP_E_ARG;
         const uint64_t len = (uint64_t)en[idx[j]] - st[idx[j]] + 1;
         pref[j] = c->q11_placed ? (qrep.count(idx[j]) ? 1 : 0)
-                                : (c->host_regions && c->h_emulated[idx[j]] == 1 ? 1 : 0);
+                  : c->head_placed ? (hsoff[idx[j]] != kHeadNoScores ? 1 : 0)
+                                   : (c->host_regions && c->h_emulated[idx[j]] == 1 ? 1 : 0);
         if (wide && !pref[j]) {
             pref[j] = 2;
             any_fill = true;
@@ -3197,10 +3576,11 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
     HIPCHK(hipMemcpyAsync(d_off, off.data(), n * 8, hipMemcpyHostToDevice, c->stream));
     for (size_t j = 0; j < n; ++j) {
         if (pref[j] != 1) continue;
-        const uint64_t so = c->q11_placed ? qrep[idx[j]] : c->h_score_off[idx[j]];
+        const uint64_t so = c->q11_placed ? qrep[idx[j]] : c->head_placed ? hsoff[idx[j]] : c->h_score_off[idx[j]];
         if (so == ~0ull) return UP_E_INTERNAL;
         const uint64_t len = (uint64_t)en[idx[j]] - st[idx[j]] + 1;
-        HIPCHK(hipMemcpyAsync(d_slab + off[j], c->d_emu_scores.p + so, 2 * len * sizeof(double),
+        const double *scores = c->head_placed ? ps.d_k0_scores.p : c->d_emu_scores.p;  // the completed slot's slab
+        HIPCHK(hipMemcpyAsync(d_slab + off[j], scores + so, 2 * len * sizeof(double),
                               hipMemcpyDeviceToDevice, c->stream));
     }
     HIPCHK(hipMemcpyAsync(d_pref, pref.data(), n + 1, hipMemcpyHostToDevice, c->stream));
@@ -3248,6 +3628,7 @@ int up_timings(up_ctx *c, double *ms, int n) {
     if (!c || !ms) return UP_E_ARG;
     for (int i = 0; i < n && i < 5; ++i) ms[i] = c->times[i];
     if (n > 5) ms[5] = c->prof_ms;
+    for (int i = 6; i < n && i < 8; ++i) ms[i] = c->head_ms[i - 6];
     return UP_OK;
 }
 
@@ -3344,6 +3725,13 @@ int up_set_profile_capture(up_ctx *c, int on) {
     if (!c) return UP_E_ARG;
     if (busy(c)) return UP_E_STATE;
     c->prof_capture = on != 0;
+    return UP_OK;
+}
+
+int up_set_head_place(up_ctx *c, int on) {
+    if (!c) return UP_E_ARG;
+    if (busy(c)) return UP_E_STATE;
+    c->head_place = on != 0;
     return UP_OK;
 }
 

@@ -95,6 +95,12 @@ struct EmuParams {
     // chains as ranges of one buffer's unit list (segmented replay): group g
     // walks gunits[gbeg[g] .. gend[g]) -- null: goff's ranges
     const uint32_t *gbeg, *gend;
+    // head units placed inside the pass (headplace.hip): records emitted per
+    // unit so far, and per record its emission index within its unit (the
+    // host merge's stable sort by unit, recovered without the host) -- null:
+    // not recorded
+    uint32_t *unit_n;
+    uint32_t *out_rank;
 };
 
 constexpr uint32_t kFlushEvent = 0xFFFFFFFFu;
@@ -274,6 +280,8 @@ __device__ static void emu_region(const EmuParams &P, EmuState &E, EmuLds &L) {
     }
     if (keep && lane == 0) {
         if (P.out_group) P.out_group[slot] = E.group;
+        // (one wave walks a unit and emits in order: the count so far is the rank)
+        if (P.unit_n) P.out_rank[slot] = atomicAdd(&P.unit_n[E.cur_unit], 1u);
         up_region &o = P.out[slot];
         o.unit = E.cur_unit;
         o.left = E.left;
