@@ -47,10 +47,10 @@ def _run(cmd, cwd=ROOT):
 
 
 def compile_lib(out, extra=(), jobs=None):
-    """libunipeak_hip.so from six translation units compiled in parallel:
-    api.hip (C-ABI, non-templated kernels), tir.hip (tags_in_regions) and
-    nh_tu.hip once per window width NH = 1..8 (the templated K1/K3/K4
-    kernels)."""
+    """libunipeak_hip.so from eleven translation units compiled in parallel:
+    api.hip (C-ABI, non-templated kernels), tir.hip (tags_in_regions),
+    countmap.hip (convert_align) and nh_tu.hip once per window width
+    NH = 1..8 (the templated K1/K3/K4 kernels)."""
     from concurrent.futures import ThreadPoolExecutor
     csrc = os.path.join(ROOT, "unipeak_amd", "csrc")
     objdir = os.path.join(ROOT, "build", "obj_" + os.path.basename(out).replace(".so", ""))

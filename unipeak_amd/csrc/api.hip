@@ -12,11 +12,14 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/unipeak_hip.h"
+#include "devmem.h"
 #include "kernels.h"
 
 #include "kernels.hip"  // device code shared with the per-NH units (nh_tu.hip)
@@ -28,90 +31,27 @@
 #include "wide.hip"
 
 namespace upk {
-// the templated K1 / K3 / K4 kernels live in four translation units, one per
-// window width NH (nh_tu.hip, built in parallel); these return their addresses
-const void *scan_kernel_nh1(int, bool, bool, int);
-const void *scan_kernel_nh2(int, bool, bool, int);
-const void *scan_kernel_nh3(int, bool, bool, int);
-const void *scan_kernel_nh4(int, bool, bool, int);
-const void *scan_kernel_nh5(int, bool, bool, int);
-const void *scan_kernel_nh6(int, bool, bool, int);
-const void *scan_kernel_nh7(int, bool, bool, int);
-const void *scan_kernel_nh8(int, bool, bool, int);
-const void *exact1_kernel_nh1();
-const void *exact1_kernel_nh2();
-const void *exact1_kernel_nh3();
-const void *exact1_kernel_nh4();
-const void *exact1_kernel_nh5();
-const void *exact1_kernel_nh6();
-const void *exact1_kernel_nh7();
-const void *exact1_kernel_nh8();
-const void *stats_kernel_nh1(int, bool, int);
-const void *stats_kernel_nh2(int, bool, int);
-const void *stats_kernel_nh3(int, bool, int);
-const void *stats_kernel_nh4(int, bool, int);
-const void *stats_kernel_nh5(int, bool, int);
-const void *stats_kernel_nh6(int, bool, int);
-const void *stats_kernel_nh7(int, bool, int);
-const void *stats_kernel_nh8(int, bool, int);
-const void *shift_kernel_nh1(int);
-const void *shift_kernel_nh2(int);
-const void *shift_kernel_nh3(int);
-const void *shift_kernel_nh4(int);
-const void *shift_kernel_nh5(int);
-const void *shift_kernel_nh6(int);
-const void *shift_kernel_nh7(int);
-const void *shift_kernel_nh8(int);
+// the templated K1 / K3 / K4 kernels live in eight translation units, one per
+// window width NH (nh_tu.hip, built in parallel); each returns the selectors
+// of its kernels' addresses
+WidthKernels width_kernels_nh1(), width_kernels_nh2(), width_kernels_nh3(), width_kernels_nh4(),
+    width_kernels_nh5(), width_kernels_nh6(), width_kernels_nh7(), width_kernels_nh8();
 // window words on each side of an output word: ceil((bw + 1) / 64)
 static int window_nh(int bw) { return (bw + 64) / 64; }
-static const void *exact1_kernel_for(int bw) {
-    switch (window_nh(bw)) {
-    case 1: return exact1_kernel_nh1();
-    case 2: return exact1_kernel_nh2();
-    case 3: return exact1_kernel_nh3();
-    case 4: return exact1_kernel_nh4();
-    case 5: return exact1_kernel_nh5();
-    case 6: return exact1_kernel_nh6();
-    case 7: return exact1_kernel_nh7();
-    default: return exact1_kernel_nh8();
-    }
+static const WidthKernels &width_kernels(int bw) {
+    static const WidthKernels tab[8] = {width_kernels_nh1(), width_kernels_nh2(), width_kernels_nh3(),
+                                        width_kernels_nh4(), width_kernels_nh5(), width_kernels_nh6(),
+                                        width_kernels_nh7(), width_kernels_nh8()};
+    return tab[std::min(window_nh(bw), 8) - 1];  // (bw >= 0: at least one word)
 }
+static const void *exact1_kernel_for(int bw) { return width_kernels(bw).exact1(); }
 static const void *scan_kernel_for(int bw, int pool, bool nd, bool prof, int mode) {
-    switch (window_nh(bw)) {
-    case 1: return scan_kernel_nh1(pool, nd, prof, mode);
-    case 2: return scan_kernel_nh2(pool, nd, prof, mode);
-    case 3: return scan_kernel_nh3(pool, nd, prof, mode);
-    case 4: return scan_kernel_nh4(pool, nd, prof, mode);
-    case 5: return scan_kernel_nh5(pool, nd, prof, mode);
-    case 6: return scan_kernel_nh6(pool, nd, prof, mode);
-    case 7: return scan_kernel_nh7(pool, nd, prof, mode);
-    default: return scan_kernel_nh8(pool, nd, prof, mode);
-    }
+    return width_kernels(bw).scan(pool, nd, prof, mode);
 }
 static const void *stats_kernel_for(int bw, int pool, bool nd, int one) {
-    switch (window_nh(bw)) {
-    case 1: return stats_kernel_nh1(pool, nd, one);
-    case 2: return stats_kernel_nh2(pool, nd, one);
-    case 3: return stats_kernel_nh3(pool, nd, one);
-    case 4: return stats_kernel_nh4(pool, nd, one);
-    case 5: return stats_kernel_nh5(pool, nd, one);
-    case 6: return stats_kernel_nh6(pool, nd, one);
-    case 7: return stats_kernel_nh7(pool, nd, one);
-    default: return stats_kernel_nh8(pool, nd, one);
-    }
+    return width_kernels(bw).stats(pool, nd, one);
 }
-static const void *shift_kernel_for(int bw, int pool) {
-    switch (window_nh(bw)) {
-    case 1: return shift_kernel_nh1(pool);
-    case 2: return shift_kernel_nh2(pool);
-    case 3: return shift_kernel_nh3(pool);
-    case 4: return shift_kernel_nh4(pool);
-    case 5: return shift_kernel_nh5(pool);
-    case 6: return shift_kernel_nh6(pool);
-    case 7: return shift_kernel_nh7(pool);
-    default: return shift_kernel_nh8(pool);
-    }
-}
+static const void *shift_kernel_for(int bw, int pool) { return width_kernels(bw).shift(pool); }
 }  // namespace upk
 
 using namespace upk;
@@ -122,7 +62,7 @@ struct Unit {
     uint32_t len = 0;
     int32_t nstrands = 1;
     int32_t buffer = 0;
-    uint8_t *dptr = nullptr;   // 4-bit tracks (kernels.h)
+    DevBuf<uint8_t> dptr;      // 4-bit tracks (kernels.h); the per-unit buffers are exact-sized (alloc_exact)
     uint64_t stride = 0;       // bytes per track
     uint32_t nstrips = 0;
     uint32_t strip0 = 0;
@@ -130,11 +70,11 @@ struct Unit {
     bool has_override = false;
     // counts >= kEsc per track: position -> count (authoritative copy)
     std::vector<std::map<uint32_t, uint32_t>> ovf;
-    uint64_t *d_ovf = nullptr;     // uploaded entries, sorted by (track, pos)
-    uint32_t *d_ovf_off = nullptr; // [ntracks + 1]
-    uint32_t *d_ovf_tidx = nullptr;  // [ntracks][nblk] escape tile per block (kNoTile: none)
-    uint8_t *d_ovf_tiles = nullptr;  // [ntiles][kOvfBlk]
-    uint8_t *d_pct = nullptr;        // pooled count track (POOL 1; UnitDesc::pct)
+    DevBuf<uint64_t> d_ovf;        // uploaded entries, sorted by (track, pos)
+    DevBuf<uint32_t> d_ovf_off;    // [ntracks + 1]
+    DevBuf<uint32_t> d_ovf_tidx;   // [ntracks][nblk] escape tile per block (kNoTile: none)
+    DevBuf<uint8_t> d_ovf_tiles;   // [ntiles][kOvfBlk]
+    DevBuf<uint8_t> d_pct;         // pooled count track (POOL 1; UnitDesc::pct)
     bool ovf_dirty = false;
     bool cs_dirty = false;     // a track changed: rebuild its chunk-sum plane (csum_kernel)
     bool pool_dirty = true;    // rebuild the unit's pooled plane (pool_kernel)
@@ -142,60 +82,17 @@ struct Unit {
     uint32_t pad_bw = 0;           // the widest kernel the track padding covers (unit_stride)
 };
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t want) {
-        if (want <= n && p) return hipSuccess;
-        // growth is rare (first passes); a pipelined pass may still read p
-        if (p) (void)hipDeviceSynchronize();
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        size_t cap = want < 16 ? 16 : want + want / 4;
-        hipError_t e = hipMalloc(&p, cap * sizeof(T));
-        if (e == hipSuccess) n = cap;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-// pinned, device-mapped host memory: kernels write results straight into it
-// (coherent, so the writes are visible to the host once the stream syncs)
-template <typename T>
-struct HostBuf {
-    T *p = nullptr;    // host address
-    T *dev = nullptr;  // device address of the same memory
-    size_t n = 0;
-    hipError_t ensure(size_t want) {
-        if (want <= n && p) return hipSuccess;
-        if (p) (void)hipDeviceSynchronize();
-        if (p) (void)hipHostFree(p);
-        p = dev = nullptr;
-        n = 0;
-        size_t cap = want < 16 ? 16 : want + want / 4;
-        hipError_t e = hipHostMalloc((void **)&p, cap * sizeof(T), hipHostMallocMapped | hipHostMallocCoherent);
-        if (e != hipSuccess) return e;
-        e = hipHostGetDevicePointer((void **)&dev, p, 0);
-        if (e == hipSuccess) n = cap;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = dev = nullptr;
-        n = 0;
-    }
-};
+static_assert(!std::is_copy_constructible_v<DevBuf<int>>, "a copied owner would free twice");
+// (so std::vector<Unit> moves its elements when it reallocates)
+static_assert(std::is_nothrow_move_constructible_v<Unit>, "Unit must move without throwing");
 
 constexpr int kSlots = UP_MAX_IN_FLIGHT;  // passes in flight at most (up_run_async)
 
 }  // namespace
 
+// Every buffer, event, stream and graph below frees itself (devmem.h).
+// up_close drains every stream before the destructor runs, so the order of
+// the members carries no meaning.
 struct up_ctx {
     int dev = 0;
     int ncu = 0;                     // compute units of the device
@@ -216,14 +113,14 @@ struct up_ctx {
     // first), the rest of a pass on one of n_chain chain streams in turn, so
     // that many passes' K1x..K3 may overlap (bench.py raises
     // GPU_MAX_HW_QUEUES so no two of them share a hardware queue)
-    hipStream_t k1a_stream = nullptr;
-    hipStream_t chain[4] = {};
+    Stream k1a_stream;
+    Stream chain[4];
     // chain streams in use (UNIPEAK_CHAINS, 1..4): three -- hg19 configs[1],
     // same box, two alternating rounds: 4,832 / 4,755 Gbp/s vs 4,652 / 4,487
     // with two and 4,636 / 4,604 with four
     int n_chain = 3;
     uint64_t nlaunch = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
     bool have_params = false;
     up_params p{};
     std::vector<uint8_t> ctl;
@@ -271,7 +168,7 @@ struct up_ctx {
     uint64_t nreg = 0;
     bool ran = false;
     std::vector<uint32_t> unit_last;
-    hipEvent_t ev[8] = {};
+    Event ev[8];
     double times[5] = {0, 0, 0, 0, 0};
     double prof_ms = 0;  // the dense-profile kernel of the last up_unit_profile* (HIP events)
     int timing = 2;                  // up_set_timing: 0 wall only, 1 + K1a, 2 every phase
@@ -281,11 +178,11 @@ struct up_ctx {
     // starts once the previous pass's K1a has ended, k1a_end); several slots
     // let the host enqueue passes while earlier ones are still completing
     struct Pass {
-        hipStream_t stream = nullptr;
-        hipEvent_t k1a_end = nullptr;   // this pass's K1a finished
+        hipStream_t stream = nullptr;   // the chain stream of this pass (owned by the context)
+        Event k1a_end;                  // this pass's K1a finished
         // K1x..K3 of the pass as hipGraphs, one per launch-argument set
         // (record targets rotate), most recent first
-        std::vector<std::pair<std::vector<uint8_t>, hipGraphExec_t>> graphs;
+        std::vector<std::pair<std::vector<uint8_t>, GraphExec>> graphs;
         bool counters_armed = false;    // xcount / ovf_count are zero (re-armed by K2b)
         DevBuf<uint64_t> d_info;
         DevBuf<uint32_t> d_rec, d_ovf_count, d_ovf_rec, d_head;
@@ -305,17 +202,6 @@ struct up_ctx {
         DevBuf<double> d_k0_scores;
         DevBuf<HeadPlace> d_hp_tab;
         DevBuf<uint32_t> d_hp_st, d_hp_en, d_hp_un;
-        void release() {
-            d_hp_stage.release(); d_k0_out.release(); d_hp_stage_cnt.release(); d_k0_counts.release();
-            d_k0_rank.release(); d_k0_ctr.release(); d_k0_units.release(); d_k0_score_off.release();
-            d_hp_soff.release(); d_k0_scores.release(); d_hp_tab.release(); d_hp_st.release();
-            d_hp_en.release(); d_hp_un.release();
-            d_info.release(); d_rec.release(); d_ovf_count.release(); d_ovf_rec.release(); d_head.release();
-            d_cnt.release(); d_nreg.release(); d_bsum.release(); d_starts.release(); d_ends.release();
-            d_runit.release(); d_peak_pos.release(); d_xlist.release(); d_xcount.release();
-            d_xwcount.release(); d_xref.release(); d_peak_val.release(); d_spk.release(); d_corr.release();
-            d_wcorr.release(); d_wslab.release();
-        }
         uint8_t *target = nullptr;   // record target of this pass (device address) or null
         void *target_hostp = nullptr;// host address of a host target
         uint64_t target_cap = 0;
@@ -343,9 +229,9 @@ struct up_ctx {
         int k3_kind = -1;            // the K3 dispatch_stats picks for this pass (up_last_stats_kind)
         int scan_kind = -1;          // the scan this pass launches: 0 K1, 1 K1w, 2 K1q (up_last_scan_kind)
         std::chrono::steady_clock::time_point t0;
-        hipEvent_t ev[5] = {};       // K1a begin, K1a end, K1b end, K2 end, K3 end
-        hipEvent_t hev[3] = {};      // a placed pass at timing level 2: K0 begin, K0 end, placement end
-        hipEvent_t done = nullptr;
+        Event ev[5];                 // K1a begin, K1a end, K1b end, K2 end, K3 end
+        Event hev[3];                // a placed pass at timing level 2: K0 begin, K0 end, placement end
+        Event done;
     } pass[kSlots];
     uint64_t seq_launched = 0, seq_done = 0;
     int cur_slot = 0;                // slot of the last completed pass (host records)
@@ -360,7 +246,7 @@ struct up_ctx {
     std::deque<int> lq;              // slots to launch, in order
     bool lbusy = false, lstop = false, use_launcher = true;
     // head-hit (quirk Q1) replay
-    hipEvent_t host_work = nullptr;  // marks work on `stream` that a pass must follow
+    Event host_work;                 // marks work on `stream` that a pass must follow
     DevBuf<uint32_t> d_resync, d_emu_n, d_emu_err, d_emu_counts, d_ring_hits, d_reg_hit, d_reg_hits;
     DevBuf<int32_t> d_unit_buffer;
     DevBuf<uint32_t> d_gunits, d_goff;  // K0 chain groups (emulate_units)
@@ -410,7 +296,7 @@ struct up_ctx {
     uint32_t hp_ngroups = 0;
     DevBuf<uint32_t> d_hp_head, d_hp_gunits, d_hp_goff;
     DevBuf<int32_t> d_hp_ubuf;
-    hipEvent_t k0_done = nullptr;
+    Event k0_done;
     bool k0_done_set = false;
     HostBuf<uint32_t> hp_resync[kSlots];
     // threshold <= 0 through K1q (run_q11): the blocking pass in progress,
@@ -448,7 +334,7 @@ struct up_ctx {
     // up_unit_scatter staging: two mapped host buffers the scatter kernel
     // reads directly, reused once the event of their previous use fired
     HostBuf<uint32_t> hp_scat[2];
-    hipEvent_t scat_ev[2] = {};
+    Event scat_ev[2];
     int scat_i = 0;
     uint64_t reg_cap = 1u << 16;  // record capacity of one pass (grown on demand)
     uint8_t *target = nullptr;    // device address of the caller's record buffer
@@ -471,7 +357,7 @@ static void index_stale(up_ctx *c) { c->passes_on_tracks = 0; }
 static void sync_all(up_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     (void)hipStreamSynchronize(c->k1a_stream);
-    for (auto st : c->chain)
+    for (hipStream_t st : c->chain)
         if (st) (void)hipStreamSynchronize(st);
 }
 
@@ -579,7 +465,8 @@ int up_open(int hip_device, up_ctx **out) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return UP_E_NODEV;
     if (hip_device < 0 || hip_device >= n) return UP_E_ARG;
-    up_ctx *c = new up_ctx();
+    // (a HIPCHK that fails below frees the context and what it holds so far)
+    std::unique_ptr<up_ctx> c(new up_ctx());
     c->dev = hip_device;
     HIPCHK(hipSetDevice(hip_device));
     HIPCHK(hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, hip_device));
@@ -621,19 +508,11 @@ int up_open(int hip_device, up_ctx **out) {
     HIPCHK(hipEventCreateWithFlags(&c->host_work, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->k0_done, hipEventDisableTiming));
     for (auto &e : c->scat_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    *out = c;
+    *out = c.release();
     return UP_OK;
 }
 
 static void free_units(up_ctx *c) {
-    for (auto &u : c->units) {
-        if (u.dptr) (void)hipFree(u.dptr);
-        if (u.d_ovf) (void)hipFree(u.d_ovf);
-        if (u.d_ovf_off) (void)hipFree(u.d_ovf_off);
-        if (u.d_ovf_tidx) (void)hipFree(u.d_ovf_tidx);
-        if (u.d_ovf_tiles) (void)hipFree(u.d_ovf_tiles);
-        if (u.d_pct) (void)hipFree(u.d_pct);
-    }
     c->units.clear();
     c->units_dirty = true;
     c->ran = false;
@@ -649,48 +528,10 @@ void up_close(up_ctx *c) {
     (void)hipSetDevice(c->dev);
     (void)hipStreamSynchronize(c->stream);
     sync_all(c);
-    free_units(c);
+    for (auto &e : c->scat_ev) (void)hipEventSynchronize(e);
     drop_target(c);
     for (void *h : c->host_regs) (void)hipHostUnregister(h);
-    c->d_kern.release(); c->d_coef.release(); c->d_nc.release(); c->d_ctl.release();
-    c->d_units.release(); c->d_unit_last.release();
-    c->d_resync.release(); c->d_emu_n.release(); c->d_emu_err.release();
-    c->d_emu_counts.release(); c->d_ring_hits.release(); c->d_reg_hit.release(); c->d_reg_hits.release();
-    c->d_unit_buffer.release(); c->d_reg_f.release(); c->d_reg_r.release(); c->d_emu_out.release();
-    c->d_ring_f.release(); c->d_ring_r.release(); c->d_ring_has.release();
-    c->d_emu_scores.release(); c->d_emu_score_off.release(); c->d_emu_nscores.release();
-    c->d_sh_idx.release(); c->d_sh_off.release(); c->d_sh_slab.release(); c->d_sh_out.release();
-    c->d_sh_pref.release();
-    c->d_pf_unit.release(); c->d_pf_event.release(); c->d_pf_pos.release(); c->d_pf_score.release();
-    c->d_pf_n.release();
-    c->d_gunits.release(); c->d_goff.release(); c->d_gskip.release(); c->d_gstop.release();
-    c->d_emu_group.release(); c->d_q11_head.release();
-    c->d_seg.release(); c->d_seg_n.release(); c->d_gbeg.release(); c->d_gend.release();
-    c->d_q11_stage.release(); c->d_q11_stage_cnt.release(); c->d_q11_tab.release(); c->d_q11_scr.release();
-    c->d_q11_edit.release(); c->d_q11_st.release(); c->d_q11_en.release(); c->d_q11_src.release();
-    for (int k = 0; k < kSlots; ++k) {
-        c->hp_regions[k].release(); c->hp_counts[k].release(); c->hp_status[k].release(); c->hp_head[k].release();
-        for (auto &e : c->pass[k].ev) (void)hipEventDestroy(e);
-        for (auto &e : c->pass[k].hev) (void)hipEventDestroy(e);
-        (void)hipEventDestroy(c->pass[k].done);
-        (void)hipEventDestroy(c->pass[k].k1a_end);
-        for (auto &g : c->pass[k].graphs) (void)hipGraphExecDestroy(g.second);
-        c->pass[k].release();
-    }
-    (void)hipStreamDestroy(c->k1a_stream);
-    for (auto st : c->chain)
-        if (st) (void)hipStreamDestroy(st);
-    (void)hipEventDestroy(c->host_work);
-    (void)hipEventDestroy(c->k0_done);
-    c->d_hp_head.release(); c->d_hp_gunits.release(); c->d_hp_goff.release(); c->d_hp_ubuf.release();
-    for (auto &h : c->hp_resync) h.release();
-    for (auto &e : c->scat_ev) (void)hipEventSynchronize(e);
-    c->hp_scat[0].release(); c->hp_scat[1].release();
-    for (auto &e : c->scat_ev) (void)hipEventDestroy(e);
-    c->d_wscreen.release(); c->d_stage.release(); c->d_dbg.release(); c->d_pack_ovf.release(); c->d_pack_n.release();
-    for (auto &e : c->ev) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // its members free the device memory, events, streams and graphs
 }
 
 static void set_q_params(up_ctx *c);
@@ -885,10 +726,9 @@ int up_add_unit(up_ctx *c, uint32_t len, int32_t nstrands, int32_t buffer_id, ui
     // the unit's pooled plane
     const size_t bytes = u.stride * (size_t)c->p.n_samples * nstrands / 4 * 5 + u.stride / 4;
     u.ovf.resize((size_t)c->p.n_samples * nstrands);
-    hipError_t e = hipMalloc(&u.dptr, bytes);
-    if (e != hipSuccess) return UP_E_NOMEM;
-    HIPCHK(hipMemsetAsync(u.dptr, 0, bytes, c->stream));
-    c->units.push_back(u);
+    if (u.dptr.alloc_exact(bytes) != hipSuccess) return UP_E_NOMEM;
+    HIPCHK(hipMemsetAsync(u.dptr.p, 0, bytes, c->stream));
+    c->units.push_back(std::move(u));
     c->units_dirty = true;
     c->ran = false;
     if (unit_id) *unit_id = (uint32_t)(c->units.size() - 1);
@@ -912,7 +752,7 @@ int up_reset_units(up_ctx *c) {
 
 static uint8_t *track_ptr(up_ctx *c, uint32_t unit, int strand, uint16_t sample) {
     const Unit &u = c->units[unit];
-    return u.dptr + ((uint64_t)strand * c->p.n_samples + sample) * u.stride;
+    return u.dptr.p + ((uint64_t)strand * c->p.n_samples + sample) * u.stride;
 }
 
 static int check_track(up_ctx *c, uint32_t unit, int32_t strand, uint16_t sample) {
@@ -1076,17 +916,7 @@ int up_unit_synth_ex(up_ctx *c, uint32_t unit, int32_t strand, uint16_t sample, 
     uint32_t *trk = c->d_stage.p;  // dense uint32 staging, packed below
     HIPCHK(hipMemsetAsync(trk, 0, (size_t)len * sizeof(uint32_t), c->stream));
     const uint64_t npos = (uint64_t)(hi - lo + 1);
-    // device scratch of this call, freed on every return path after the
-    // stream has drained (an early HIPCHK return included)
-    struct StreamScratch {
-        hipStream_t s;
-        void *p[2] = {nullptr, nullptr};
-        ~StreamScratch() {
-            if (p[0] || p[1]) (void)hipStreamSynchronize(s);
-            for (void *q : p)
-                if (q) (void)hipFree(q);
-        }
-    } scratch{c->stream};
+    StreamScratch scratch(c->stream);
     uint64_t tab[1024];
     if (!peak_seed) {
         hipLaunchKernelGGL(synth_bg_kernel, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0,
@@ -1100,10 +930,10 @@ int up_unit_synth_ex(up_ctx *c, uint32_t unit, int32_t strand, uint16_t sample, 
             pr *= mu / (double)(k + 1);
             cdf += pr;
         }
-        HIPCHK(hipMalloc(&scratch.p[0], sizeof tab));
-        const uint64_t *d_tab = (const uint64_t *)scratch.p[0];
+        uint64_t *d_tab = nullptr;
+        HIPCHK(scratch.alloc(&d_tab, sizeof tab));
         // stream-ordered, then waited for: the source is this stack frame
-        HIPCHK(hipMemcpyAsync(scratch.p[0], tab, sizeof tab, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_tab, tab, sizeof tab, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         const uint32_t nch = (uint32_t)((npos + 65535) >> 16);
         hipLaunchKernelGGL(synth_bgc_kernel, dim3((nch + 255) / 256), dim3(256), 0, c->stream, trk,
@@ -1146,8 +976,8 @@ int up_unit_synth_ex(up_ctx *c, uint32_t unit, int32_t strand, uint16_t sample, 
             }
         }
         if (!tags.empty()) {
-            HIPCHK(hipMalloc(&scratch.p[1], tags.size() * sizeof(uint32_t)));
-            uint32_t *d = (uint32_t *)scratch.p[1];
+            uint32_t *d = nullptr;
+            HIPCHK(scratch.alloc(&d, tags.size() * sizeof(uint32_t)));
             HIPCHK(hipMemcpyAsync(d, tags.data(), tags.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
             hipLaunchKernelGGL(synth_peak_kernel, dim3((unsigned)((tags.size() + 255) / 256)), dim3(256), 0,
                                c->stream, trk, d, (uint64_t)tags.size());
@@ -1165,8 +995,9 @@ int up_unit_tag_total(up_ctx *c, uint32_t unit, int32_t strand, uint16_t sample,
     if (r) return r;
     if (!total) return UP_E_ARG;
     HIPCHK(hipSetDevice(c->dev));
+    StreamScratch scratch(c->stream);
     unsigned long long *d = nullptr;
-    HIPCHK(hipMalloc(&d, sizeof(unsigned long long)));
+    HIPCHK(scratch.alloc(&d, sizeof(unsigned long long)));
     HIPCHK(hipMemsetAsync(d, 0, sizeof(unsigned long long), c->stream));
     const Unit &u = c->units[unit];
     hipLaunchKernelGGL(track_sum_kernel, dim3(1024), dim3(256), 0, c->stream,
@@ -1175,7 +1006,6 @@ int up_unit_tag_total(up_ctx *c, uint32_t unit, int32_t strand, uint16_t sample,
     unsigned long long h = 0;
     HIPCHK(hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    (void)hipFree(d);
     for (const auto &kv : u.ovf[(size_t)strand * c->p.n_samples + sample]) h += kv.second;
     *total = h;
     return UP_OK;
@@ -1224,18 +1054,16 @@ static int regrow_unit(up_ctx *c, Unit &u) {
     const int S = c->p.n_samples;
     const uint64_t stride = unit_stride(u.len, c->p.bw);
     const size_t bytes = stride * (size_t)S * u.nstrands / 4 * 5 + stride / 4;
-    uint8_t *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return UP_E_NOMEM;
-    HIPCHK(hipMemsetAsync(p, 0, bytes, c->stream));
-    HIPCHK(hipMemcpy2DAsync(p, stride, u.dptr, u.stride, u.stride, (size_t)S * u.nstrands, hipMemcpyDeviceToDevice,
-                            c->stream));
+    DevBuf<uint8_t> grown;
+    if (grown.alloc_exact(bytes) != hipSuccess) return UP_E_NOMEM;
+    HIPCHK(hipMemsetAsync(grown.p, 0, bytes, c->stream));
+    HIPCHK(hipMemcpy2DAsync(grown.p, stride, u.dptr.p, u.stride, u.stride, (size_t)S * u.nstrands,
+                            hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    (void)hipFree(u.dptr);
-    u.dptr = p;
+    u.dptr = std::move(grown);
     u.stride = stride;
     u.pad_bw = std::max<uint32_t>(c->p.bw, kMaxBw);
-    if (u.d_pct) (void)hipFree(u.d_pct);
-    u.d_pct = nullptr;
+    u.d_pct.release();
     u.cs_dirty = u.pool_dirty = true;
     return UP_OK;
 }
@@ -1261,14 +1089,10 @@ static int sync_layout(up_ctx *c) {
         u.strip0 = strip;
         strip += u.nstrips;
         if (u.ovf_dirty) {
-            if (u.d_ovf) (void)hipFree(u.d_ovf);
-            if (u.d_ovf_off) (void)hipFree(u.d_ovf_off);
-            if (u.d_ovf_tidx) (void)hipFree(u.d_ovf_tidx);
-            if (u.d_ovf_tiles) (void)hipFree(u.d_ovf_tiles);
-            u.d_ovf = nullptr;
-            u.d_ovf_off = nullptr;
-            u.d_ovf_tidx = nullptr;
-            u.d_ovf_tiles = nullptr;
+            u.d_ovf = {};
+            u.d_ovf_off = {};
+            u.d_ovf_tidx = {};
+            u.d_ovf_tiles = {};
             // entries sorted by (track, position), indexed per kOvfBlk positions
             std::vector<uint64_t> e;
             u.ovf_max = 0;
@@ -1297,20 +1121,20 @@ static int sync_layout(up_ctx *c) {
                 while (b <= nb) o[b++] = (uint32_t)e.size();
             }
             if (!e.empty()) {
-                HIPCHK(hipMalloc(&u.d_ovf, e.size() * sizeof(uint64_t)));
-                HIPCHK(hipMalloc(&u.d_ovf_off, off.size() * sizeof(uint32_t)));
-                HIPCHK(hipMalloc(&u.d_ovf_tidx, tidx.size() * sizeof(uint32_t)));
-                HIPCHK(hipMalloc(&u.d_ovf_tiles, tiles.size()));
-                HIPCHK(hipMemcpy(u.d_ovf, e.data(), e.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(u.d_ovf_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(u.d_ovf_tidx, tidx.data(), tidx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(u.d_ovf_tiles, tiles.data(), tiles.size(), hipMemcpyHostToDevice));
+                HIPCHK(u.d_ovf.alloc_exact(e.size()));
+                HIPCHK(u.d_ovf_off.alloc_exact(off.size()));
+                HIPCHK(u.d_ovf_tidx.alloc_exact(tidx.size()));
+                HIPCHK(u.d_ovf_tiles.alloc_exact(tiles.size()));
+                HIPCHK(hipMemcpy(u.d_ovf.p, e.data(), e.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(u.d_ovf_off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(u.d_ovf_tidx.p, tidx.data(), tidx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(u.d_ovf_tiles.p, tiles.data(), tiles.size(), hipMemcpyHostToDevice));
             }
             u.ovf_dirty = false;
         }
-        d[i] = UnitDesc{(uint64_t)(uintptr_t)u.dptr, u.stride, u.len, u.strip0, u.nstrips, u.nstrands,
-                        (uint64_t)(uintptr_t)u.d_ovf, (uint64_t)(uintptr_t)u.d_ovf_off,
-                        (uint64_t)(uintptr_t)u.d_ovf_tidx, (uint64_t)(uintptr_t)u.d_ovf_tiles, 0};
+        d[i] = UnitDesc{(uint64_t)(uintptr_t)u.dptr.p, u.stride, u.len, u.strip0, u.nstrips, u.nstrands,
+                        (uint64_t)(uintptr_t)u.d_ovf.p, (uint64_t)(uintptr_t)u.d_ovf_off.p,
+                        (uint64_t)(uintptr_t)u.d_ovf_tidx.p, (uint64_t)(uintptr_t)u.d_ovf_tiles.p, 0};
     }
     c->nstrips = strip;
     c->ovf_max_all = 0;
@@ -1371,7 +1195,7 @@ static int sync_index(up_ctx *c) {
     const bool pooled = c->p.nondir || pool_mode(c) != 0;
     bool stale = false;
     for (const Unit &u : c->units)
-        stale |= u.cs_dirty || (pooled && u.pool_dirty) || (want_pct && !u.d_pct) || (!want_pct && u.d_pct);
+        stale |= u.cs_dirty || (pooled && u.pool_dirty) || (want_pct && !u.d_pct.p) || (!want_pct && u.d_pct.p);
     if (want && stale) {
         if (busy(c)) settle_in_flight(c);  // (UP_INDEX_AUTO's second pass: the first one ran without it)
         const int S = c->p.n_samples;
@@ -1380,12 +1204,11 @@ static int sync_index(up_ctx *c) {
         std::vector<uint8_t *> pt;
         for (size_t i = 0; i < c->units.size(); ++i) {
             Unit &u = c->units[i];
-            if (want_pct && !u.d_pct) {
-                HIPCHK(hipMalloc(&u.d_pct, (size_t)u.nstrands * kPerByte * u.stride));
+            if (want_pct && !u.d_pct.p) {
+                HIPCHK(u.d_pct.alloc_exact((size_t)u.nstrands * kPerByte * u.stride));
                 u.pool_dirty = true;
-            } else if (!want_pct && u.d_pct) {
-                (void)hipFree(u.d_pct);
-                u.d_pct = nullptr;
+            } else if (!want_pct) {
+                u.d_pct = {};
             }
             if (u.cs_dirty) {
                 lc.push_back((uint32_t)i);
@@ -1395,10 +1218,10 @@ static int sync_index(up_ctx *c) {
             if (pooled && u.pool_dirty) {
                 lp.push_back((uint32_t)i);
                 op.push_back(op.back() + u.stride / 16);
-                if (u.d_pct) {
+                if (u.d_pct.p) {
                     lt.push_back((uint32_t)i);
                     ot.push_back(ot.back() + u.stride / 4 * (uint64_t)u.nstrands);
-                    pt.push_back(u.d_pct);
+                    pt.push_back(u.d_pct.p);
                 }
             }
         }
@@ -1444,7 +1267,7 @@ static int sync_index(up_ctx *c) {
     if (on != c->index_on) {
         if (busy(c)) settle_in_flight(c);  // passes in flight read the unit table
         for (size_t i = 0; i < c->units.size(); ++i)
-            c->h_units[i].pct = on ? (uint64_t)(uintptr_t)c->units[i].d_pct : 0;
+            c->h_units[i].pct = on ? (uint64_t)(uintptr_t)c->units[i].d_pct.p : 0;
         if (!c->h_units.empty())
             HIPCHK(hipMemcpy(c->d_units.p, c->h_units.data(), c->h_units.size() * sizeof(UnitDesc),
                              hipMemcpyHostToDevice));
@@ -1466,6 +1289,21 @@ static int pool_mode(const up_ctx *c) {
     if (c->nc.size() == 1) return 0;
     const double cmax = (double)std::max<uint32_t>(kEsc - 1, c->ovf_max_all) * (double)c->nc.size();
     return cmax < 4294967296.0 ? 1 : 2;
+}
+
+// f(std::integral_constant<int, POOL>{}) for the pooling mode pm (0, 1 or 2),
+// f(std::bool_constant<B>{}) for a flag: a kernel's template arguments from
+// run-time values, with the launch written once
+template <typename F>
+static void with_pool_mode(int pm, F &&f) {
+    if (pm == 0) f(std::integral_constant<int, 0>{});
+    else if (pm == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 2>{});
+}
+template <typename F>
+static void with_flag(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 // pooled count tracks (UnitDesc::pct) for this pooling; UNIPEAK_PCT=0: off
@@ -2486,19 +2324,11 @@ static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatPar
         const unsigned blocks = wide_corr_blocks(c);
         const size_t lds = corr_lds_bytes(c->p.bw);
         const uint32_t lcap = wide_list_cap();
-        const int pm = pool_mode(c);
-        if (pm == 0)
-            hipLaunchKernelGGL(wide_corr_kernel<0>, dim3(blocks), dim3(64), lds, ps.stream, SP, ps.d_starts.p,
-                               ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, (uint64_t)cap, ps.d_wslab.p, lcap,
-                               ps.d_wcorr.p);
-        else if (pm == 1)
-            hipLaunchKernelGGL(wide_corr_kernel<1>, dim3(blocks), dim3(64), lds, ps.stream, SP, ps.d_starts.p,
-                               ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, (uint64_t)cap, ps.d_wslab.p, lcap,
-                               ps.d_wcorr.p);
-        else
-            hipLaunchKernelGGL(wide_corr_kernel<2>, dim3(blocks), dim3(64), lds, ps.stream, SP, ps.d_starts.p,
-                               ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, (uint64_t)cap, ps.d_wslab.p, lcap,
-                               ps.d_wcorr.p);
+        with_pool_mode(pool_mode(c), [&](auto pm) {
+            hipLaunchKernelGGL(wide_corr_kernel<decltype(pm)::value>, dim3(blocks), dim3(64), lds, ps.stream, SP,
+                               ps.d_starts.p, ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, (uint64_t)cap, ps.d_wslab.p,
+                               lcap, ps.d_wcorr.p);
+        });
         HIPCHK(hipGetLastError());
     }
     dispatch_stats(c, ps.stream, P, std::max<uint64_t>(ps.req_last_nreg, 1024));
@@ -2666,14 +2496,12 @@ static int launch_pass(up_ctx *c, int slot) {
         if (c->p.bw > kMaxBw) {  // K1w: screen + exact in one (wide.hip)
             graph = false;
             const unsigned blocks = std::max(1u, std::min<uint32_t>(ns, 8192));
-            const int pm = pool_mode(c);
-            if (c->p.nondir) {
-                if (pm == 0) hipLaunchKernelGGL((wide_kernel<0, true>), dim3(blocks), dim3(64), 0, s1, SP);
-                else if (pm == 1) hipLaunchKernelGGL((wide_kernel<1, true>), dim3(blocks), dim3(64), 0, s1, SP);
-                else hipLaunchKernelGGL((wide_kernel<2, true>), dim3(blocks), dim3(64), 0, s1, SP);
-            } else if (pm == 0) hipLaunchKernelGGL((wide_kernel<0, false>), dim3(blocks), dim3(64), 0, s1, SP);
-            else if (pm == 1) hipLaunchKernelGGL((wide_kernel<1, false>), dim3(blocks), dim3(64), 0, s1, SP);
-            else hipLaunchKernelGGL((wide_kernel<2, false>), dim3(blocks), dim3(64), 0, s1, SP);
+            with_flag(c->p.nondir != 0, [&](auto nd) {
+                with_pool_mode(pool_mode(c), [&](auto pm) {
+                    hipLaunchKernelGGL((wide_kernel<decltype(pm)::value, decltype(nd)::value>), dim3(blocks),
+                                       dim3(64), 0, s1, SP);
+                });
+            });
         } else {
             // K1a: stream + screen -- the chunk-sum plane when the index is
             // on, else the 2-bit fields (one-pass cost: no derived data read)
@@ -2748,15 +2576,12 @@ static int launch_pass(up_ctx *c, int slot) {
             return r;
         }
         HIPCHK(e);
-        hipGraphExec_t x = nullptr;
+        GraphExec x;
         const hipError_t ei = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
         HIPCHK(ei);
-        if (ps.graphs.size() >= 8) {  // keep the most recent ones
-            (void)hipGraphExecDestroy(ps.graphs.back().second);
-            ps.graphs.pop_back();
-        }
-        ps.graphs.insert(ps.graphs.begin(), {key, x});
+        if (ps.graphs.size() >= 8) ps.graphs.pop_back();  // keep the most recent ones
+        ps.graphs.emplace(ps.graphs.begin(), key, std::move(x));
         gi = 0;
     }
     HIPCHK(hipGraphLaunch(ps.graphs[gi].second, ps.stream));
@@ -3591,16 +3416,10 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
         ScanParams SP = scan_params(c, ps, c->ovf_cap);  // (units, pooling and kernel weights only)
         const size_t wl = corr_lds_bytes(c->p.bw);
         const uint32_t nn = (uint32_t)n, lcap = wide_list_cap();
-        const int pm = pool_mode(c);
-        if (pm == 0)
-            hipLaunchKernelGGL(wide_fill_kernel<0>, dim3(blocks), dim3(64), wl, c->stream, SP, ps.d_starts.p,
-                               ps.d_ends.p, ps.d_runit.p, d_idx, nn, d_off, d_pref, d_slab, lcap);
-        else if (pm == 1)
-            hipLaunchKernelGGL(wide_fill_kernel<1>, dim3(blocks), dim3(64), wl, c->stream, SP, ps.d_starts.p,
-                               ps.d_ends.p, ps.d_runit.p, d_idx, nn, d_off, d_pref, d_slab, lcap);
-        else
-            hipLaunchKernelGGL(wide_fill_kernel<2>, dim3(blocks), dim3(64), wl, c->stream, SP, ps.d_starts.p,
-                               ps.d_ends.p, ps.d_runit.p, d_idx, nn, d_off, d_pref, d_slab, lcap);
+        with_pool_mode(pool_mode(c), [&](auto pm) {
+            hipLaunchKernelGGL(wide_fill_kernel<decltype(pm)::value>, dim3(blocks), dim3(64), wl, c->stream, SP,
+                               ps.d_starts.p, ps.d_ends.p, ps.d_runit.p, d_idx, nn, d_off, d_pref, d_slab, lcap);
+        });
         HIPCHK(hipGetLastError());
     }
     {
@@ -3644,8 +3463,9 @@ int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t cou
     const Unit &u = c->units[unit];
     const uint64_t dom = (uint64_t)u.nstrips * kStrip;  // scan domain incl. Q16 tail
     if (first + count - 1 > dom) return UP_E_ARG;
+    StreamScratch scratch(c->stream);
     double *d = nullptr;
-    HIPCHK(hipMalloc(&d, 2 * (size_t)count * sizeof(double) + 16));
+    HIPCHK(scratch.alloc(&d, 2 * (size_t)count * sizeof(double) + 16));
     HIPCHK(hipMemsetAsync(d, 0, 2 * (size_t)count * sizeof(double), c->stream));
     ScanParams P = scan_params(c, c->pass[0], c->ovf_cap);  // no pass in flight; records unused
     P.prof_f = d;
@@ -3659,14 +3479,13 @@ int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t cou
         const uint64_t nstretch = ((first + count - 2) / 64 - (first - 1) / 64) / kProfWords + 1;
         const dim3 grid((unsigned)std::min<uint64_t>(nstretch, 1u << 16));
         const size_t lds = prof_lds_bytes(c->p.bw);
-        const int pm = pool_mode(c);
-        if (c->p.nondir) {  // f and r, each its own ascending sum (up_set_wide_nd_full: check_runnable)
-            if (pm == 0) hipLaunchKernelGGL((wide_profile_kernel<0, true>), grid, dim3(64), lds, c->stream, P, cap);
-            else if (pm == 1) hipLaunchKernelGGL((wide_profile_kernel<1, true>), grid, dim3(64), lds, c->stream, P, cap);
-            else hipLaunchKernelGGL((wide_profile_kernel<2, true>), grid, dim3(64), lds, c->stream, P, cap);
-        } else if (pm == 0) hipLaunchKernelGGL((wide_profile_kernel<0, false>), grid, dim3(64), lds, c->stream, P, cap);
-        else if (pm == 1) hipLaunchKernelGGL((wide_profile_kernel<1, false>), grid, dim3(64), lds, c->stream, P, cap);
-        else hipLaunchKernelGGL((wide_profile_kernel<2, false>), grid, dim3(64), lds, c->stream, P, cap);
+        // (nondirectional: f and r, each its own ascending sum -- up_set_wide_nd_full: check_runnable)
+        with_flag(c->p.nondir != 0, [&](auto nd) {
+            with_pool_mode(pool_mode(c), [&](auto pm) {
+                hipLaunchKernelGGL((wide_profile_kernel<decltype(pm)::value, decltype(nd)::value>), grid, dim3(64),
+                                   lds, c->stream, P, cap);
+            });
+        });
     } else {
         const uint32_t s0 = u.strip0 + (uint32_t)((first - 1) / kStrip);
         const uint32_t s1 = u.strip0 + (uint32_t)((first + count - 2) / kStrip) + 1;
@@ -3682,7 +3501,6 @@ int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t cou
     }
     HIPCHK(hipMemcpy(out_f, d, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
     if (out_r) HIPCHK(hipMemcpy(out_r, d + count, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
-    (void)hipFree(d);
     return UP_OK;
 }
 
@@ -3696,12 +3514,10 @@ int up_unit_profile(up_ctx *c, uint32_t unit, double *out_f, double *out_r, uint
 int up_hbm_copy_gbps(up_ctx *c, uint64_t bytes, int reps, double *gbps) {
     if (!c || !gbps || bytes < 16 || bytes % 16 || reps < 1) return UP_E_ARG;
     HIPCHK(hipSetDevice(c->dev));
+    StreamScratch scratch(c->stream);
     void *a = nullptr, *b = nullptr;
-    HIPCHK(hipMalloc(&a, bytes));
-    if (hipMalloc(&b, bytes) != hipSuccess) {
-        (void)hipFree(a);
-        return UP_E_NOMEM;
-    }
+    HIPCHK(scratch.alloc(&a, bytes));
+    if (scratch.alloc(&b, bytes) != hipSuccess) return UP_E_NOMEM;
     HIPCHK(hipMemsetAsync(a, 1, bytes, c->stream));
     float best = 0;
     for (int i = 0; i <= reps; ++i) {
@@ -3714,8 +3530,6 @@ int up_hbm_copy_gbps(up_ctx *c, uint64_t bytes, int reps, double *gbps) {
         (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[6]);
         if (i > 0 && (best == 0 || ms < best)) best = ms;  // first copy is a warm-up
     }
-    (void)hipFree(a);
-    (void)hipFree(b);
     *gbps = 2.0 * (double)bytes / (best * 1e-3) / 1e9;
     return UP_OK;
 }

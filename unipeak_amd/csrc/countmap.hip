@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/unipeak_hip.h"
+#include "devmem.h"
 
 namespace {
 
@@ -157,46 +158,28 @@ __global__ void __launch_bounds__(kThreads) cm_emit(const uint32_t *__restrict__
     }
 }
 
-template <typename T>
-struct Dev {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t want) {
-        if (want <= n && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        const size_t cap = want < 16 ? 16 : want;
-        hipError_t e = hipMalloc(&p, cap * sizeof(T));
-        if (e == hipSuccess) n = cap;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
+using upk::DevBuf;  // (sized by the data here: ensure_exact, no slack)
 
 }  // namespace
 
+// (up_cm_close drains the stream before the members free themselves)
 struct up_cm {
     int dev = 0;
-    hipStream_t stream = nullptr;
+    upk::Stream stream;
     uint32_t n_contigs = 0;
     uint64_t genome = 0;             // positions per strand (sum of contig lengths)
     std::vector<uint64_t> off;       // [n_contigs + 1] first position of each contig
-    Dev<uint32_t> tracks;            // [2 * genome]
-    Dev<uint64_t> d_off;
-    Dev<uint32_t> d_len, d_err;
-    Dev<uint32_t> a_contig, a_pos, a_cnt;  // add staging
-    Dev<uint8_t> a_fwd;
-    Dev<uint32_t> bcount;
-    Dev<uint64_t> boff;
-    Dev<uint32_t> o_contig, o_pos, o_cnt;
-    Dev<uint8_t> o_fwd;
+    DevBuf<uint32_t> tracks;            // [2 * genome]
+    DevBuf<uint64_t> d_off;
+    DevBuf<uint32_t> d_len, d_err;
+    DevBuf<uint32_t> a_contig, a_pos, a_cnt;  // add staging
+    DevBuf<uint8_t> a_fwd;
+    DevBuf<uint32_t> bcount;
+    DevBuf<uint64_t> boff;
+    DevBuf<uint32_t> o_contig, o_pos, o_cnt;
+    DevBuf<uint8_t> o_fwd;
     double ms_add = 0, ms_collect = 0;
-    hipEvent_t ev[2] = {};
+    upk::Event ev[2];
 };
 
 #define CMCHK(x)                                                                      \
@@ -227,9 +210,9 @@ int up_cm_open(int hip_device, uint32_t n_contigs, const uint32_t *contig_len, u
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(UP_E_HIP);
     for (auto &e : h->ev)
         if (hipEventCreate(&e) != hipSuccess) return fail(UP_E_HIP);
-    if (h->tracks.ensure(2 * h->genome + 4) != hipSuccess) return fail(UP_E_NOMEM);
-    if (h->d_off.ensure(n_contigs + 1) != hipSuccess || h->d_len.ensure(n_contigs) != hipSuccess ||
-        h->d_err.ensure(1) != hipSuccess)
+    if (h->tracks.ensure_exact(2 * h->genome + 4) != hipSuccess) return fail(UP_E_NOMEM);
+    if (h->d_off.ensure_exact(n_contigs + 1) != hipSuccess || h->d_len.ensure_exact(n_contigs) != hipSuccess ||
+        h->d_err.ensure_exact(1) != hipSuccess)
         return fail(UP_E_NOMEM);
     if (hipMemsetAsync(h->tracks.p, 0, (2 * h->genome + 4) * sizeof(uint32_t), h->stream) != hipSuccess ||
         hipMemsetAsync(h->d_err.p, 0, sizeof(uint32_t), h->stream) != hipSuccess ||
@@ -247,16 +230,6 @@ void up_cm_close(up_cm *h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto *b : {&h->tracks, &h->d_len, &h->d_err, &h->a_contig, &h->a_pos, &h->a_cnt, &h->bcount,
-                    &h->o_contig, &h->o_pos, &h->o_cnt})
-        b->release();
-    h->d_off.release();
-    h->boff.release();
-    h->a_fwd.release();
-    h->o_fwd.release();
-    for (auto &e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -266,10 +239,10 @@ int up_cm_add(up_cm *h, uint64_t n, const uint32_t *contig, const uint32_t *pos,
     if (n == 0) return UP_OK;
     CMCHK(hipSetDevice(h->dev));
     hipStream_t st = h->stream;
-    CMCHK(h->a_contig.ensure(n));
-    CMCHK(h->a_pos.ensure(n));
-    CMCHK(h->a_fwd.ensure(n));
-    if (count) CMCHK(h->a_cnt.ensure(n));
+    CMCHK(h->a_contig.ensure_exact(n));
+    CMCHK(h->a_pos.ensure_exact(n));
+    CMCHK(h->a_fwd.ensure_exact(n));
+    if (count) CMCHK(h->a_cnt.ensure_exact(n));
     CMCHK(hipMemcpyAsync(h->a_contig.p, contig, n * 4, hipMemcpyHostToDevice, st));
     CMCHK(hipMemcpyAsync(h->a_pos.p, pos, n * 4, hipMemcpyHostToDevice, st));
     CMCHK(hipMemcpyAsync(h->a_fwd.p, forward, n, hipMemcpyHostToDevice, st));
@@ -296,8 +269,8 @@ int up_cm_collect(up_cm *h, int nondir, uint64_t *n, uint32_t *contig, uint32_t 
     hipStream_t st = h->stream;
     const uint64_t view_n = nondir ? h->genome : 2 * h->genome;
     const uint64_t nblk = (view_n + kBlockPos - 1) / kBlockPos;
-    CMCHK(h->bcount.ensure(nblk + 1));
-    CMCHK(h->boff.ensure(nblk + 1));
+    CMCHK(h->bcount.ensure_exact(nblk + 1));
+    CMCHK(h->boff.ensure_exact(nblk + 1));
     CMCHK(hipEventRecord(h->ev[0], st));
     if (nblk)
         hipLaunchKernelGGL(cm_count, dim3((uint32_t)nblk), dim3(kThreads), 0, st, h->tracks.p, h->genome,
@@ -313,10 +286,10 @@ int up_cm_collect(up_cm *h, int nondir, uint64_t *n, uint32_t *contig, uint32_t 
     if (!contig && !pos && !count && !forward) return UP_OK;
     if (!contig || !pos || !count || !forward) return UP_E_ARG;
     if (cap < total) return UP_E_NOMEM;
-    CMCHK(h->o_contig.ensure(total + 1));
-    CMCHK(h->o_pos.ensure(total + 1));
-    CMCHK(h->o_cnt.ensure(total + 1));
-    CMCHK(h->o_fwd.ensure(total + 1));
+    CMCHK(h->o_contig.ensure_exact(total + 1));
+    CMCHK(h->o_pos.ensure_exact(total + 1));
+    CMCHK(h->o_cnt.ensure_exact(total + 1));
+    CMCHK(h->o_fwd.ensure_exact(total + 1));
     CMCHK(hipMemcpyAsync(h->boff.p, bo.data(), (nblk + 1) * 8, hipMemcpyHostToDevice, st));
     if (nblk)
         hipLaunchKernelGGL(cm_emit, dim3((uint32_t)nblk), dim3(kThreads), 0, st, h->tracks.p, h->genome,

@@ -210,4 +210,14 @@ struct StatParams {
                            // set: K3 keeps K1w's peaks, runs no KDE of its own and takes corr from it
 };
 
+// The templated K1 / K3 / K4 kernels of one window width NH: selectors that
+// return the address of the instantiation to launch (host side; nh_tu.hip
+// defines one set per width, api.hip indexes them by the bandwidth)
+struct WidthKernels {
+    const void *(*scan)(int pool, bool nd, bool prof, int mode);  // K1a / K1b / the profile kernel
+    const void *(*exact1)();                                      // K1b for one directional sample
+    const void *(*stats)(int pool, bool nd, int one);             // K3
+    const void *(*shift)(int pool);                               // K4
+};
+
 }  // namespace upk

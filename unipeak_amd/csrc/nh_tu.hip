@@ -1,8 +1,9 @@
 // unipeak_amd/csrc/nh_tu.hip -- one translation unit per window width NH
 // (= ceil((bw + 1) / 64) words on each side, 1..8): compiled eight times with
 // -DUPK_NH_TU=1..8, so the templated K1 / K3 / K4 kernels of the eight widths
-// build in parallel.  Each unit exports the addresses of its kernels; api.hip
-// launches them with hipLaunchKernel (kernels.hip holds the code).
+// build in parallel.  Each unit exports one accessor, the selectors of its
+// kernels' addresses (kernels.h WidthKernels); api.hip launches them with
+// hipLaunchKernel (kernels.hip holds the code).
 #include "kernels.hip"
 #include "stats1.hip"
 #include "exact1.hip"
@@ -34,7 +35,7 @@ static const void *scan_ptr(bool prof, int mode) {
 // K1: the variants the library launches -- K1a (screen: over the chunk-sum
 // plane or, without the index, the 2-bit fields), K1b (exact) and the
 // profile kernel (PROF, fused) -- for every pool mode and strand layout
-const void *UPK_CAT(scan_kernel_nh, UPK_NH_TU)(int pool, bool nd, bool prof, int mode) {
+static const void *scan_sel(int pool, bool nd, bool prof, int mode) {
     if (nd) {
         if (pool == 0) return scan_ptr<0, true>(prof, mode);
         if (pool == 1) return scan_ptr<1, true>(prof, mode);
@@ -46,11 +47,11 @@ const void *UPK_CAT(scan_kernel_nh, UPK_NH_TU)(int pool, bool nd, bool prof, int
 }
 
 // K1b for one pooled directional sample with the Q keys on (exact1.hip)
-const void *UPK_CAT(exact1_kernel_nh, UPK_NH_TU)() { return (const void *)exact1_kernel<kNH>; }
+static const void *exact1_sel() { return (const void *)exact1_kernel<kNH>; }
 
 // K3 (one: one pooled directional sample with K1b's peaks, stats1.hip --
 // 1: a wave per region, 2: a lane per region)
-const void *UPK_CAT(stats_kernel_nh, UPK_NH_TU)(int pool, bool nd, int one) {
+static const void *stats_sel(int pool, bool nd, int one) {
     if (one == 2) return (const void *)stats1L_kernel<kNH>;
     if (one) return (const void *)stats1_kernel<kNH>;
     if (nd) {
@@ -64,10 +65,12 @@ const void *UPK_CAT(stats_kernel_nh, UPK_NH_TU)(int pool, bool nd, int one) {
 }
 
 // K4
-const void *UPK_CAT(shift_kernel_nh, UPK_NH_TU)(int pool) {
+static const void *shift_sel(int pool) {
     if (pool == 0) return (const void *)shift_kernel<kNH, 0>;
     if (pool == 1) return (const void *)shift_kernel<kNH, 1>;
     return (const void *)shift_kernel<kNH, 2>;
 }
+
+WidthKernels UPK_CAT(width_kernels_nh, UPK_NH_TU)() { return {scan_sel, exact1_sel, stats_sel, shift_sel}; }
 
 }  // namespace upk

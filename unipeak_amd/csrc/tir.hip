@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/unipeak_hip.h"
+#include "devmem.h"
 
 namespace {
 
@@ -330,58 +331,28 @@ __global__ void __launch_bounds__(256) tir_query(const StreamView *__restrict__ 
     hits[t] = v.psum[e] - v.psum[s];
 }
 
-template <typename T>
-struct Dev {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t want) {
-        if (want <= n && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        const size_t cap = want < 16 ? 16 : want;
-        hipError_t e = hipMalloc(&p, cap * sizeof(T));
-        if (e == hipSuccess) n = cap;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
+using upk::DevBuf;  // (sized by the data here: ensure_exact, no slack)
 
 struct DevStream {
     uint32_t n = 0;
     bool ready = false;
-    Dev<uint64_t> key;
-    Dev<uint8_t> fwd;
-    Dev<uint32_t> cnt, psum, run_end, next_f, next_r, agg, total;
-    void release() {
-        key.release();
-        fwd.release();
-        cnt.release();
-        psum.release();
-        run_end.release();
-        next_f.release();
-        next_r.release();
-        agg.release();
-        total.release();
-        ready = false;
-    }
+    DevBuf<uint64_t> key;
+    DevBuf<uint8_t> fwd;
+    DevBuf<uint32_t> cnt, psum, run_end, next_f, next_r, agg, total;
 };
 
 }  // namespace
 
+// (up_tir_close drains the stream before the members free themselves)
 struct up_tir {
     int dev = 0;
-    hipStream_t stream = nullptr;
+    upk::Stream stream;
     std::vector<DevStream> streams;
-    Dev<StreamView> d_views;
-    Dev<uint32_t> d_rc, d_rl, d_rr, d_first, d_end, d_hits;
-    Dev<uint8_t> d_rf;
+    DevBuf<StreamView> d_views;
+    DevBuf<uint32_t> d_rc, d_rl, d_rr, d_first, d_end, d_hits;
+    DevBuf<uint8_t> d_rf;
     float last_ms[2] = {0, 0};  // [0] stream preparation (all set_stream), [1] last query
-    hipEvent_t ev[2] = {};
+    upk::Event ev[2];
 };
 
 #define TIRCHK(x)                                                                    \
@@ -414,18 +385,6 @@ void up_tir_close(up_tir *h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto &s : h->streams) s.release();
-    h->d_views.release();
-    h->d_rc.release();
-    h->d_rl.release();
-    h->d_rr.release();
-    h->d_rf.release();
-    h->d_first.release();
-    h->d_end.release();
-    h->d_hits.release();
-    for (auto &e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -438,15 +397,15 @@ int up_tir_set_stream(up_tir *h, uint32_t stream, uint64_t n, const uint64_t *ke
     DevStream &d = h->streams[stream];
     d.n = (uint32_t)n;
     const uint32_t nblk = (uint32_t)((n + kBlock - 1) / kBlock);
-    TIRCHK(d.key.ensure(n));
-    TIRCHK(d.fwd.ensure(n));
-    TIRCHK(d.cnt.ensure(n));
-    TIRCHK(d.psum.ensure(n + 1));
-    TIRCHK(d.run_end.ensure(n + 1));
-    TIRCHK(d.next_f.ensure(n + 1));
-    TIRCHK(d.next_r.ensure(n + 1));
-    TIRCHK(d.agg.ensure(4ull * nblk + 4));
-    TIRCHK(d.total.ensure(1));
+    TIRCHK(d.key.ensure_exact(n));
+    TIRCHK(d.fwd.ensure_exact(n));
+    TIRCHK(d.cnt.ensure_exact(n));
+    TIRCHK(d.psum.ensure_exact(n + 1));
+    TIRCHK(d.run_end.ensure_exact(n + 1));
+    TIRCHK(d.next_f.ensure_exact(n + 1));
+    TIRCHK(d.next_r.ensure_exact(n + 1));
+    TIRCHK(d.agg.ensure_exact(4ull * nblk + 4));
+    TIRCHK(d.total.ensure_exact(1));
     hipStream_t st = h->stream;
     if (n) {
         TIRCHK(hipMemcpyAsync(d.key.p, key, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -493,14 +452,14 @@ int up_tir_query(up_tir *h, uint32_t n_streams, uint64_t n_regions, const uint32
         views[s] = StreamView{d.key.p, d.fwd.p, d.psum.p, d.run_end.p, d.next_f.p, d.next_r.p, d.n, 0};
     }
     const uint64_t RS = n_regions * n_streams;
-    TIRCHK(h->d_views.ensure(n_streams));
-    TIRCHK(h->d_rc.ensure(n_regions));
-    TIRCHK(h->d_rl.ensure(n_regions));
-    TIRCHK(h->d_rr.ensure(n_regions));
-    TIRCHK(h->d_rf.ensure(n_regions));
-    TIRCHK(h->d_first.ensure(RS));
-    TIRCHK(h->d_end.ensure(RS));
-    TIRCHK(h->d_hits.ensure(RS));
+    TIRCHK(h->d_views.ensure_exact(n_streams));
+    TIRCHK(h->d_rc.ensure_exact(n_regions));
+    TIRCHK(h->d_rl.ensure_exact(n_regions));
+    TIRCHK(h->d_rr.ensure_exact(n_regions));
+    TIRCHK(h->d_rf.ensure_exact(n_regions));
+    TIRCHK(h->d_first.ensure_exact(RS));
+    TIRCHK(h->d_end.ensure_exact(RS));
+    TIRCHK(h->d_hits.ensure_exact(RS));
     hipStream_t st = h->stream;
     TIRCHK(hipMemcpyAsync(h->d_views.p, views.data(), n_streams * sizeof(StreamView), hipMemcpyHostToDevice, st));
     TIRCHK(hipMemcpyAsync(h->d_rc.p, contig, n_regions * 4, hipMemcpyHostToDevice, st));
