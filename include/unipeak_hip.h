@@ -190,9 +190,16 @@ int up_reset_units(up_ctx *ctx);
  * UNIPEAK_WIDE_ND=0 (read at up_open, for A/B runs), it takes the replay
  * below.  Wider kernels (32768..65535, where
  * the reference's UShort retirement count wraps, misc/peakcall.cpp:172-177)
- * take the whole-buffer replay.  A negative coefficient at a threshold <= 0,
+ * take the whole-buffer replay.  bw > 511 (up to 32767) with a threshold
+ * <= 0 on directional units with the -w capture off and no coefficient below
+ * 0 runs wide K1q: the runs of processed positions and their peaks from
+ * parallel kernels (wide_runs_kernel, wide_peak_kernel), K2 / K3, the
+ * placement and the head chains as for K1q, inside this blocking call only
+ * (UNIPEAK_WIDE_Q11=0, read at up_open, keeps the replay for A/B runs).
+ * A negative coefficient at a threshold <= 0,
  * the -w capture with a head unit at a threshold <= 0, and bw > 511 at a
- * threshold <= 0, from 32768 on or on nondirectional units with the -w
+ * threshold <= 0 on nondirectional units or with the -w capture on, bw from
+ * 32768 on, or nondirectional units above 511 with the -w
  * capture on run the exact
  * state machine over every unit instead (K0, as independent chains from
  * every run start, one chain per buffer with the -w capture on: exact, far
@@ -302,7 +309,8 @@ int up_last_stats_kind(up_ctx *ctx);
  * runs: the records do not depend on it. */
 int up_last_exact_kind(up_ctx *ctx);
 /* how the pass completed last found its regions: 0 K1 (K1a + K1b), 1 K1w
- * (bw above 511), 2 K1q (a threshold <= 0), 3 the exact replay of every unit
+ * (bw above 511), 2 K1q (a threshold <= 0; above bw 511 its wide form on
+ * directional units, up to 32767), 3 the exact replay of every unit
  * (K0); -1 when no pass has completed or it had no units.  The K0 chains of
  * head units inside a K1 / K1w / K1q pass do not change the value.  For
  * tests and A/B runs: the records do not depend on it. */
@@ -315,7 +323,8 @@ int up_last_scan_kind(up_ctx *ctx);
 int up_scan_density(up_ctx *ctx, uint32_t *bytes_per_1024);
 /* device-side timings of the last up_run in ms: [0]=K1 scan, [1]=K2
  * segment, [2]=K3 stats (with wide_corr_kernel, the strand correlation of a
- * nondirectional K1w pass, which runs just before K3), [3]=whole up_run wall, [4]=K1 launches; with n > 5
+ * nondirectional K1w pass, or wide K1q's peak kernels, which run just before
+ * K3; wide K1q's run kernel counts under [0]), [3]=whole up_run wall, [4]=K1 launches; with n > 5
  * also [5]=the dense-profile kernel of the last up_unit_profile* call (HIP
  * events around it); with n > 6 also [6]=K0 and [7]=the placement kernels of
  * the last pass that placed its head units itself (up_set_head_place) at
@@ -328,7 +337,9 @@ int up_timings(up_ctx *ctx, double *ms, int n);
 /* dense per-position score f+r of one unit (testing/-w): out[len].  K1's
  * fused profile path up to UP_MAX_PARALLEL_BW; wider kernels where K1w runs
  * (directional units, a threshold > 0, bw up to 32767): wide_profile_kernel,
- * every score the ascending sum K1w forms, out_r all zero.  Nondirectional
+ * every score the ascending sum K1w forms, out_r all zero; the same kernel
+ * where wide K1q runs (directional units, a threshold <= 0, the -w capture
+ * off: it does not look at the threshold).  Nondirectional
  * units above UP_MAX_PARALLEL_BW: refused by default; with
  * up_set_wide_nd_full on, the kernel's two-strand form fills out_f with
  * forwardScore and out_r with reverseScore, each its own ascending sum (the
@@ -369,7 +380,8 @@ int up_unit_profile_range(up_ctx *ctx, uint32_t unit, uint64_t first, uint32_t c
  *    kernel, up_run_async admitted (each pass slot in flight then holds its own
  *    64 MB of strand-correlation slabs when the correlation is evaluated).
  * UP_E_STATE while a pass is in flight. UNIPEAK_WIDE_ND=0 still forces the
- * replay whatever this says; a threshold <= 0 and bw >= 32768 keep the replay
+ * replay whatever this says; a threshold <= 0 (for nondirectional units: the
+ * directional ones run wide K1q) and bw >= 32768 keep the replay
  * and the refusals as well.  The records and the -w profile do not depend on
  * it; bin/regions sets it.  Making 1 the default is a later change. */
 int up_set_wide_nd_full(up_ctx *ctx, int on);

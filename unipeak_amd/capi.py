@@ -374,8 +374,9 @@ class Lib:
         return int(self.L.up_last_exact_kind(self.ctx))
 
     def last_scan_kind(self):
-        """how the pass completed last found its regions: 0 K1, 1 K1w, 2 K1q, 3 the
-        exact replay of every unit, -1 no pass or no units (up_last_scan_kind)"""
+        """how the pass completed last found its regions: 0 K1, 1 K1w, 2 K1q (above bw
+        511 its wide form), 3 the exact replay of every unit, -1 no pass or no units
+        (up_last_scan_kind)"""
         return int(self.L.up_last_scan_kind(self.ctx))
 
     def scan_density(self):

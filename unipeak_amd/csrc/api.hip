@@ -107,6 +107,7 @@ struct up_ctx {
     bool k3_one = true;              // batched K3 for one directional sample (UNIPEAK_K3_ONE=0: off)
     bool wide_nd = true;             // K1w for nondirectional units (UNIPEAK_WIDE_ND=0: the replay)
     bool wide_nd_full = false;       // those units' -w capture, dense profile and up_run_async (up_set_wide_nd_full)
+    bool wide_q11 = true;            // wide K1q: threshold <= 0 at bw 512 .. 32,767 (UNIPEAK_WIDE_Q11=0: the replay)
     bool use_graphs = true;          // passes as hipGraphs (UNIPEAK_GRAPHS=0: plain launches)
     // streams of the passes: every K1a on one high-priority stream (stream
     // order serialises them; as resources free up the dispatcher serves it
@@ -192,6 +193,11 @@ struct up_ctx {
         DevBuf<uint64_t> d_spk;          // K1 per-strip partial peaks (ScanParams::spk)
         DevBuf<double> d_corr;           // K3 (f, r) slabs for the strand correlation (-D -y)
         DevBuf<double> d_wcorr, d_wslab; // wide_corr_kernel: strandCorr(0) per region, its per-wave slabs
+        // wide K1q's peaks (wide.hip): the regions' stretch prefix, one partial per (region, stretch)
+        DevBuf<uint64_t> d_wq_off;
+        DevBuf<double> d_wq_val;
+        DevBuf<uint32_t> d_wq_pos;
+        uint64_t wq_cap = 0;             // partials the two areas hold
         // head units placed inside the pass (headplace.hip): K3's stage, K0's
         // outputs (records, exptSums, ranks, score offsets and slab; counters:
         // records, error word, scores used; per unit: resync, records), the
@@ -383,6 +389,7 @@ static bool plane_scan(const up_ctx *c);
 static int pool_mode(const up_ctx *c);
 static bool pct_mode(const up_ctx *c);
 static bool wide_mode(const up_ctx *c);
+static bool wide_q11_mode(const up_ctx *c);
 
 static bool want_index(const up_ctx *c);
 
@@ -477,6 +484,7 @@ int up_open(int hip_device, up_ctx **out) {
     if (const char *e = getenv("UNIPEAK_K3_ONE")) c->k3_one = atoi(e) != 0;
     if (const char *e = getenv("UNIPEAK_K1B_ONE")) c->k1b_one = atoi(e) != 0;
     if (const char *e = getenv("UNIPEAK_WIDE_ND")) c->wide_nd = atoi(e) != 0;
+    if (const char *e = getenv("UNIPEAK_WIDE_Q11")) c->wide_q11 = atoi(e) != 0;
     if (const char *e = getenv("UNIPEAK_K1B_BLOCKS")) c->k1b_blocks = std::max(0, atoi(e));
     if (const char *e = getenv("UNIPEAK_CHAINS")) c->n_chain = std::min(4, std::max(1, atoi(e)));
     if (const char *e = getenv("UNIPEAK_LAUNCHER")) c->use_launcher = e[0] != '0';
@@ -1179,7 +1187,7 @@ static int sync_layout(up_ctx *c) {
 // from the packed tracks.  K1w screens on the planes, so it always does.
 static bool want_index(const up_ctx *c) {
     if (kTB != 2) return false;
-    if (wide_mode(c)) return true;
+    if (wide_mode(c) || wide_q11_mode(c)) return true;  // (wide K1q's peaks screen on them as well)
     switch (c->index_policy) {
     case UP_INDEX_ALWAYS: return true;
     case UP_INDEX_NEVER: return false;
@@ -1545,8 +1553,10 @@ static void dispatch_stats(up_ctx *c, hipStream_t st, const StatParams &P, uint6
 // in parallel instead (K1q, run_q11): every processed position qualifies, so
 // regions are the runs of processed positions; units that start processing
 // at position 1 still take the replay.  UNIPEAK_Q11_REPLAY=1: always replay.
-static bool q11_mode(const up_ctx *c) {
-    if (c->p.region_thr > 0 || c->p.bw > kMaxBw || kTB != 2) return false;
+// Up to kMaxBw K1q's own run kernel (proc_runs_kernel) and K3's KDE; wider,
+// up to kMaxWideBw, wide K1q (wide_q11_mode below).
+static bool q11_scores_ok(const up_ctx *c) {
+    if (c->p.region_thr > 0 || kTB != 2) return false;
     for (double q : c->coef)
         if (!(q >= 0)) return false;
     static const bool off = [] {
@@ -1555,6 +1565,8 @@ static bool q11_mode(const up_ctx *c) {
     }();
     return !off;
 }
+
+static bool q11_mode(const up_ctx *c) { return q11_scores_ok(c) && (c->p.bw <= kMaxBw || wide_q11_mode(c)); }
 
 // UNIPEAK_Q11_HEADS=replay: units that process position 1 send the whole
 // context to the whole-buffer replay (round 4's rule; A/B and tests)
@@ -1579,11 +1591,16 @@ static bool q11_whole_replay() {
 // next unit -- only the whole-buffer replay models that (emulate.hip);
 // UNIPEAK_WIDE=0: the replay instead; UNIPEAK_WIDE_ND=0 (read at up_open):
 // the replay for nondirectional units only
-static bool wide_mode(const up_ctx *c) {
+static bool wide_on() {
     static const bool on = [] {
         const char *e = getenv("UNIPEAK_WIDE");
         return !(e && *e == '0');
     }();
+    return on;
+}
+
+static bool wide_mode(const up_ctx *c) {
+    const bool on = wide_on();
     return on && c->p.bw > kMaxBw && c->p.bw <= kMaxWideBw && kTB == 2 && c->p.region_thr > 0 &&
            (!c->p.nondir || (c->wide_nd && (!c->prof_capture || c->wide_nd_full)));
 }
@@ -1595,8 +1612,21 @@ static bool wide_mode(const up_ctx *c) {
 // correlation kernel on the pass stream, no captured graph behind K1w)
 static bool wide_nd_mode(const up_ctx *c) { return c->p.nondir && wide_mode(c); }
 
+// wide K1q (wide.hip): a threshold <= 0 with non-negative scores at kMaxBw <
+// bw <= kMaxWideBw on directional units, the -w capture off: wide_runs_kernel
+// finds the runs of processed positions, wide_peak_kernel their peaks, K2 / K3
+// / the placement and the K0 head chains follow as behind narrow K1q
+// (run_q11), so its passes too run only inside the blocking up_run.
+// Nondirectional units keep the replay: one region can span a contig and its
+// strand correlation is a sequential FP64 chain over every position.
+// UNIPEAK_WIDE_Q11=0 (read at up_open): the replay (A/B, tests).
+static bool wide_q11_mode(const up_ctx *c) {
+    return c->wide_q11 && wide_on() && q11_scores_ok(c) && c->p.bw > kMaxBw && c->p.bw <= kMaxWideBw &&
+           !c->p.nondir && !c->prof_capture;
+}
+
 static bool replay_mode(const up_ctx *c) {
-    return (c->p.bw > kMaxBw && !wide_mode(c)) || (!(c->p.region_thr > 0) && !q11_mode(c));
+    return (c->p.bw > kMaxBw && !wide_mode(c) && !wide_q11_mode(c)) || (!(c->p.region_thr > 0) && !q11_mode(c));
 }
 
 static int check_params(up_ctx *c) {
@@ -1613,7 +1643,7 @@ static int check_runnable(up_ctx *c, bool profile = false) {
     if (r) return r;
     if (replay_mode(c)) return UP_E_UNSUPPORTED;
     // (the dense profile's window is K1's, or wide_profile_kernel's where K1w runs)
-    if (profile && c->p.bw > kMaxBw && !wide_mode(c)) return UP_E_UNSUPPORTED;
+    if (profile && c->p.bw > kMaxBw && !wide_mode(c) && !wide_q11_mode(c)) return UP_E_UNSUPPORTED;
     if (wide_nd_mode(c) && !c->wide_nd_full && (profile || !c->wide_nd_run)) return UP_E_UNSUPPORTED;
     return q11_mode(c) && !c->q11_run && !profile ? UP_E_UNSUPPORTED : UP_OK;
 }
@@ -2319,6 +2349,24 @@ static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatPar
                        c->hp_status[slot].dev, thdr);
     HIPCHK(hipGetLastError());
     if (events) HIPCHK(hipEventRecord(ps.ev[3], ps.stream));
+    if (ps.req_q11 && c->p.bw > kMaxBw) {  // wide K1q: every region's peak (wide.hip) into the arrays K3
+                                           // reads as known peaks (timed with K3: up_timings [2])
+        const uint32_t lcap = wide_list_cap();
+        const size_t lds = prof_lds_bytes(c->p.bw);
+        const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ps.wq_cap, 8192));
+        hipLaunchKernelGGL(wide_peak_prefix_kernel, dim3(1), dim3(1024), 0, ps.stream, ps.d_starts.p, ps.d_ends.p,
+                           ps.d_nreg.p, (uint64_t)cap, ps.d_wq_off.p);
+        with_pool_mode(pool_mode(c), [&](auto pm) {
+            hipLaunchKernelGGL(wide_peak_kernel<decltype(pm)::value>, dim3(blocks), dim3(64), lds, ps.stream, SP,
+                               ps.d_starts.p, ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, (uint64_t)cap,
+                               ps.d_wq_off.p, lcap, ps.d_wq_val.p, ps.d_wq_pos.p, ps.wq_cap);
+        });
+        const unsigned mblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((cap + 3) / 4, 1024));
+        hipLaunchKernelGGL(wide_peak_merge_kernel, dim3(mblocks), dim3(256), 0, ps.stream, ps.d_nreg.p,
+                           (uint64_t)cap, ps.d_wq_off.p, ps.d_wq_val.p, ps.d_wq_pos.p, ps.wq_cap, ps.d_peak_pos.p,
+                           ps.d_peak_val.p);
+        HIPCHK(hipGetLastError());
+    }
     if (P.corr_in) {  // -D -y behind K1w: strandCorr(0) of every region (wide.hip), K3 takes it
                       // (timed with K3: up_timings [2])
         const unsigned blocks = wide_corr_blocks(c);
@@ -2390,6 +2438,16 @@ static int launch_pass(up_ctx *c, int slot) {
     if (wcorr) {
         HIPCHK(ps.d_wcorr.ensure(cap + 1));
         HIPCHK(ps.d_wslab.ensure((size_t)wide_corr_blocks(c) * 2 * kCorrSlab));
+    }
+    if (ps.req_q11 && c->p.bw > kMaxBw) {
+        // the regions of a unit are disjoint, so their stretches of 4,096
+        // positions number at most positions / 4,096 + 2 per region: the area
+        // cannot overflow while the regions fit, and a pass that outgrows
+        // reg_cap is rerun with this area grown with it (up_run_wait)
+        ps.wq_cap = (uint64_t)ns * (kStrip / (kProfWords * 64)) + 2 * cap + 2;
+        HIPCHK(ps.d_wq_off.ensure(cap + 2));
+        HIPCHK(ps.d_wq_val.ensure(ps.wq_cap));
+        HIPCHK(ps.d_wq_pos.ensure(ps.wq_cap));
     }
     if (!ps.req_target) {
         HIPCHK(c->hp_regions[slot].ensure(cap + 1));
@@ -2481,17 +2539,32 @@ static int launch_pass(up_ctx *c, int slot) {
     c->k1a_waves = 0;
     if (ps.req_q11) {  // K1q: runs of processed positions (threshold <= 0)
         graph = false;
-        P.peak_pos = nullptr;  // K3 runs its KDE for the peaks
-        P.peak_val = nullptr;
-        P.q11 = 1;
+        const bool wq = c->p.bw > kMaxBw;  // wide K1q (wide_q11_mode)
+        if (!wq) {
+            P.peak_pos = nullptr;  // K3 runs its KDE for the peaks
+            P.peak_val = nullptr;
+            P.q11 = 1;
+        } else {
+            // wide_peak_kernel fills peak_pos / peak_val of every region between
+            // K2 and K3 and applies the leap rule itself (the run's first
+            // position does not seed the peak): K3 takes known peaks, runs no
+            // KDE -- its window spans NH <= 8 words -- and its q11 skip has
+            // nothing left to do
+            P.q11 = 0;
+        }
         // K3 -> the device stage; q11place.hip places the records
         HIPCHK(c->d_q11_stage.ensure(cap + 1));
         HIPCHK(c->d_q11_stage_cnt.ensure((cap + 1) * S));
         P.out = c->d_q11_stage.p;
         P.out_counts = c->d_q11_stage_cnt.p;
         P.cap = cap;
-        const unsigned blocks = (unsigned)std::min<uint64_t>((ns + 3) / 4, 4096);
-        hipLaunchKernelGGL(proc_runs_kernel, dim3(std::max(1u, blocks)), dim3(256), 0, s1, SP);
+        if (wq) {  // one wave per strip
+            hipLaunchKernelGGL(wide_runs_kernel, dim3(std::max(1u, std::min<uint32_t>(ns, 8192))), dim3(64), 0, s1,
+                               SP);
+        } else {
+            const unsigned blocks = (unsigned)std::min<uint64_t>((ns + 3) / 4, 4096);
+            hipLaunchKernelGGL(proc_runs_kernel, dim3(std::max(1u, blocks)), dim3(256), 0, s1, SP);
+        }
     } else {
         if (c->p.bw > kMaxBw) {  // K1w: screen + exact in one (wide.hip)
             graph = false;

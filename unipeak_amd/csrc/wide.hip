@@ -33,7 +33,9 @@
 //  * wide_corr_kernel: strandCorr(0) of every region of a nondirectional
 //    pass, between K2 and K3 (K3's own KDE spans NH <= 8 window words);
 //  * wide_fill_kernel: the (f, r) slabs of requested regions for K4
-//    (up_shift_scan, up_shift_best).
+//    (up_shift_scan, up_shift_best);
+//  * wide_peak_kernel: the peaks of wide K1q's regions -- a threshold <= 0 on
+//    directional units, whose runs wide_runs_kernel finds (end of this file).
 
 namespace upk {
 
@@ -534,6 +536,327 @@ __global__ void __launch_bounds__(64) wide_fill_kernel(ScanParams P, const uint3
         const uint32_t len = right - left + 1;
         double *fs = slab + slab_off[j];
         wide_range_scores<POOL>(P, U, P.S, P.bw, left, right, fs, fs + len, L, cap, lane);
+    }
+}
+
+// ------------------------------------------------------------------------
+// wide K1q: the region scan of a threshold <= 0 (quirk Q11 live) for kernels
+// wider than K1q's register halo (kMaxBw < bw <= kMaxWideBw, directional
+// units, non-negative scores).  The rule is proc_runs_kernel's (kernels.hip):
+// every maximal run of processed positions -- the positions within bw of an
+// add, a tag of any sample, controls included -- is one region.  A run starts
+// at a - bw for an add a with no add in [a - 2bw - 1, a - 1] and ends at
+// a + bw for an add with none in [a + 1, a + 2bw + 1].
+//   wide_runs_kernel        one wave per strip: the strip's run boundaries in
+//                           K1b's record format with peaks unknown
+//   wide_peak_prefix_kernel per region its stretches of kProfWords words ->
+//                           the exclusive prefix the next two kernels index
+//   wide_peak_kernel        one wave per (region, stretch): the stretch's
+//                           largest score and the lowest position holding it
+//   wide_peak_merge_kernel  one wave per region: its stretches' partials ->
+//                           peak_pos / peak_val, which K3 then takes as known
+//                           peaks (no KDE of its own, as behind K1w)
+
+constexpr int64_t kWqNone = -((int64_t)1 << 40);  // no add (kWqNone before, -kWqNone after)
+
+// presence bits of the 64-position word j (positions 64 j + 1 .. 64 j + 64) of
+// unit U over every track; a word outside [1, len] holds no add and is not
+// loaded (the tracks' padding covers the last word's fields past len)
+__device__ __forceinline__ uint64_t wq_word(const UnitDesc &U, int S, int64_t j) {
+    if (j < 0 || 64 * j + 1 > (int64_t)U.len) return 0;
+    uint64_t m = 0;
+    for (int st = 0; st < U.nstrands; ++st)
+        for (int k = 0; k < S; ++k)
+            m |= nz_bits64((u32x4)((gu32x4 *)(track_u8(U, S, st, k) + fbyte(kPadPos)))[j]);
+    return m & range_bits(64 * j + 1, 1, (int64_t)U.len);
+}
+
+__device__ __forceinline__ int64_t wq_wave_max(int64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = i64max(v, (int64_t)__shfl_xor((long long)v, o));
+    return v;
+}
+__device__ __forceinline__ int64_t wq_wave_min(int64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = i64min(v, (int64_t)__shfl_xor((long long)v, o));
+    return v;
+}
+
+// the first and the last add of [lo, hi] (-kWqNone / kWqNone: none), the wave
+// together: lane l takes the words l, l + 64, ... of the range.  At most
+// 2bw + 1 positions: 1,025 words, 17 per lane at bw 32,767.
+__device__ __forceinline__ void wq_span(const UnitDesc &U, int S, int64_t lo, int64_t hi, int lane, int64_t &first,
+                                        int64_t &last) {
+    lo = i64max(lo, 1);
+    hi = i64min(hi, (int64_t)U.len);
+    int64_t f = -kWqNone, l = kWqNone;
+    if (lo <= hi) {
+        const int64_t jh = (hi - 1) >> 6;
+        for (int64_t j = ((lo - 1) >> 6) + lane; j <= jh; j += 64) {
+            const int64_t base = 64 * j + 1;
+            const uint64_t m = wq_word(U, S, j) & range_bits(base, lo, hi);
+            if (m) {
+                f = i64min(f, base + __builtin_ctzll(m));
+                l = i64max(l, base + 63 - __builtin_clzll(m));
+            }
+        }
+    }
+    first = wq_wave_min(f);
+    last = wq_wave_max(l);
+}
+
+// The add that owns a boundary of strip k sits bw away from it, up to two
+// strips from k, so the strip does not widen a halo around itself: it takes
+// the exact presence words of the two strip-sized add windows -- the adds of
+// (p0 + bw, pend + bw] can start a run in (p0, pend], those of [p0 - bw,
+// pend - bw) can end one in [p0, pend) -- five words per lane each, and the
+// previous add before the start window / the next add after the end window
+// from one span query over the 2bw + 1 positions beside it (only the
+// window's first / last add can depend on it).  The 2-bit fields answer the
+// queries, so a pass needs no index for this kernel; F0 / FL (the strip's
+// first / last position is processed) are two more span queries.
+constexpr int kWqRounds = (kStrip / 64 + 1 + kWave - 1) / kWave;  // 257 words of a window: 5 per lane
+
+__global__ void __launch_bounds__(64) wide_runs_kernel(ScanParams P) {
+    const int lane = threadIdx.x;
+    const int64_t bw = P.bw, gap = 2 * bw + 1;
+    const int S = P.S;
+    for (uint32_t strip = blockIdx.x; strip < P.nstrips; strip += gridDim.x) {
+        const uint32_t u = find_unit(P.units, P.nunits, strip);
+        const UnitDesc U = P.units[u];
+        const uint32_t local = strip - U.strip0;
+        const int64_t p0 = 1 + (int64_t)local * kStrip, pend = p0 + kStrip - 1;
+        RecList R_{0, 0, kInline};
+        int64_t none_lo, none_hi;  // (the unused end of a span query)
+        // ---- starts in (p0, pend]: the adds of [ws, we] ----
+        {
+            const int64_t ws = p0 + bw + 1, we = pend + bw;
+            const int64_t j0 = (ws - 1) >> 6;
+            int64_t carry;  // the last add before the words seen so far
+            wq_span(U, S, ws - gap, ws - 1, lane, none_lo, carry);
+#pragma unroll
+            for (int r = 0; r < kWqRounds; ++r) {
+                const int64_t j = j0 + 64 * r + lane, base = 64 * j + 1;
+                const uint64_t m = base <= we ? wq_word(U, S, j) & range_bits(base, ws, we) : 0ull;
+                int64_t v = m ? base + 63 - __builtin_clzll(m) : kWqNone;
+                for (int d = 1; d < 64; d <<= 1) {  // inclusive prefix maximum of the words' last adds
+                    const int64_t o = __shfl_up((long long)v, d);
+                    if (lane >= d && o > v) v = o;
+                }
+                const int64_t ex = __shfl_up((long long)v, 1);
+                int64_t prev = lane == 0 ? carry : i64max(ex, carry);
+                carry = i64max(carry, (int64_t)__shfl((long long)v, 63));
+                uint64_t sa = 0, mm = m;  // the word's adds that start a run
+                while (mm) {
+                    const int b = __builtin_ctzll(mm);
+                    mm &= mm - 1;
+                    const int64_t a = base + b;
+                    if (prev == kWqNone || a - prev > gap) sa |= 1ull << b;
+                    prev = a;
+                }
+                uint64_t live = __ballot(sa != 0);
+                while (live) {
+                    const int l = __builtin_ctzll(live);
+                    live &= live - 1;
+                    uint64_t bits = rl_u64(sa, l);
+                    const int64_t lbase = 64 * (j0 + 64 * r + l) + 1;
+                    while (bits) {
+                        const int b = __builtin_ctzll(bits);
+                        bits &= bits - 1;
+                        rec_start(R_, (uint32_t)(lbase + b - bw), P, strip, lane);
+                    }
+                }
+            }
+        }
+        // ---- ends in [p0, pend): the adds of [es, ee] ----
+        {
+            const int64_t es = p0 - bw, ee = pend - bw - 1;
+            const int64_t j0 = (es - 1) >> 6;  // (arithmetic shift: floor; words before position 1 hold no add)
+            int64_t carry;  // the first add after the words seen so far
+            wq_span(U, S, ee + 1, ee + gap, lane, carry, none_hi);
+            uint64_t m[kWqRounds];
+            int64_t nxt[kWqRounds];
+#pragma unroll
+            for (int r = kWqRounds - 1; r >= 0; --r) {
+                const int64_t j = j0 + 64 * r + lane, base = 64 * j + 1;
+                m[r] = base <= ee ? wq_word(U, S, j) & range_bits(base, es, ee) : 0ull;
+                int64_t v = m[r] ? base + __builtin_ctzll(m[r]) : -kWqNone;
+                for (int d = 1; d < 64; d <<= 1) {  // inclusive suffix minimum of the words' first adds
+                    const int64_t o = __shfl_down((long long)v, d);
+                    if (lane + d < 64 && o < v) v = o;
+                }
+                const int64_t ex = __shfl_down((long long)v, 1);
+                nxt[r] = lane == 63 ? carry : i64min(ex, carry);
+                carry = i64min(carry, (int64_t)__shfl((long long)v, 0));
+            }
+#pragma unroll
+            for (int r = 0; r < kWqRounds; ++r) {
+                const int64_t base = 64 * (j0 + 64 * r + lane) + 1;
+                uint64_t ea = 0, mm = m[r];  // the word's adds that end a run
+                while (mm) {
+                    const int b = __builtin_ctzll(mm);
+                    mm &= mm - 1;
+                    const int64_t nx = mm ? base + __builtin_ctzll(mm) : nxt[r];
+                    if (nx == -kWqNone || nx - (base + b) > gap) ea |= 1ull << b;
+                }
+                uint64_t live = __ballot(ea != 0);
+                while (live) {
+                    const int l = __builtin_ctzll(live);
+                    live &= live - 1;
+                    uint64_t bits = rl_u64(ea, l);
+                    const int64_t lbase = 64 * (j0 + 64 * r + l) + 1;
+                    while (bits) {
+                        const int b = __builtin_ctzll(bits);
+                        bits &= bits - 1;
+                        rec_end(R_, (uint32_t)(lbase + b + bw), 0u, -__builtin_inf(), P, strip, lane);
+                    }
+                }
+            }
+        }
+        // ---- the strip's first / last position is processed ----
+        int64_t a0, a1;
+        wq_span(U, S, p0 - bw, p0 + bw, lane, a0, none_hi);
+        wq_span(U, S, pend - bw, pend + bw, lane, a1, none_hi);
+        const bool F0 = a0 != -kWqNone, FL = a1 != -kWqNone;
+        const uint64_t info = (uint64_t)R_.ns | ((uint64_t)R_.ne << 16) | ((uint64_t)F0 << 32) |
+                              ((uint64_t)FL << 33) | ((uint64_t)(local == 0) << 34) |
+                              ((uint64_t)(local + 1 == U.nstrips) << 35) | ((uint64_t)(R_.slot != kInline) << 36);
+        if (lane == 0) P.strip_info[strip] = info;
+    }
+}
+
+// the positions a region [s, e] of starts / ends scores for its peak: s + 1 ..
+// e -- the run's first position joined by a leap with peakPos 0, so
+// Region::addPos re-seeds the peak at the next one (peakcall.cpp:76-78,
+// data.cpp:98-101; K3's StatParams::q11 states the same rule for its KDE) --
+// and the stretches of kProfWords words that cover them
+__device__ __forceinline__ int64_t wq_peak_first(uint32_t s, uint32_t e) { return e > s ? (int64_t)s + 1 : (int64_t)s; }
+__device__ __forceinline__ uint64_t wq_stretches(uint32_t s, uint32_t e) {
+    const int64_t w_first = (wq_peak_first(s, e) - 1) >> 6, w_last = ((int64_t)e - 1) >> 6;
+    return (uint64_t)((w_last - w_first) / kProfWords + 1);
+}
+
+// off[i] = the stretches of the regions before region i, off[n] = all of
+// them (n = the pass's regions, at most reg_cap).  One block of 1,024.
+__global__ void __launch_bounds__(1024) wide_peak_prefix_kernel(const uint32_t *__restrict__ starts,
+                                                                const uint32_t *__restrict__ ends,
+                                                                const uint64_t *__restrict__ nreg_p,
+                                                                uint64_t reg_cap, uint64_t *off) {
+    __shared__ uint64_t sh[16];
+    __shared__ uint64_t chunk_tot;
+    const uint64_t n = *nreg_p < reg_cap ? *nreg_p : reg_cap;
+    uint64_t base = 0;
+    for (uint64_t c0 = 0; c0 < n; c0 += 1024) {
+        const uint64_t i = c0 + threadIdx.x;
+        const uint64_t cnt = i < n ? wq_stretches(starts[i], ends[i]) : 0;
+        const uint64_t inc = block_incl_sum(cnt, sh);
+        if (i < n) off[i] = base + inc - cnt;
+        if (threadIdx.x == 1023) chunk_tot = inc;
+        __syncthreads();
+        base += chunk_tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) off[n] = base;
+}
+
+// Regions here are few and can be millions of positions long, so the work
+// items are (region, stretch) pairs: item `it` belongs to the last region r
+// with off[r] <= it (a cursor that only moves forward through the prefix).
+// Every score is the wide_stretch_scores ascending sum; the wave reduces its
+// stretch to (largest score, lowest position holding it) -> part_val /
+// part_pos[it].  No floating-point atomics.
+template <int POOL>
+__global__ void __launch_bounds__(64) wide_peak_kernel(ScanParams P, const uint32_t *__restrict__ starts,
+                                                       const uint32_t *__restrict__ ends,
+                                                       const uint32_t *__restrict__ reg_unit,
+                                                       const uint64_t *__restrict__ nreg_p, uint64_t reg_cap,
+                                                       const uint64_t *__restrict__ off, uint32_t cap,
+                                                       double *part_val, uint32_t *part_pos, uint64_t part_cap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char prof_lds[];
+    double *hcnt = (double *)prof_lds;
+    uint32_t *hpos = (uint32_t *)(prof_lds + (size_t)kProfHits * 8);
+    uint32_t *pre = hpos + kProfHits;
+    const int lane = threadIdx.x;
+    const int bw = P.bw;
+    const int S = P.S;
+    const uint64_t n = *nreg_p < reg_cap ? *nreg_p : reg_cap;
+    const uint64_t total = off[n] < part_cap ? off[n] : part_cap;
+    uint64_t cur = 0;
+    for (uint64_t it = blockIdx.x; it < total; it += gridDim.x) {
+        uint64_t hi = n;  // off[cur] <= it < off[hi]
+        while (hi - cur > 1) {
+            const uint64_t mid = (cur + hi) >> 1;
+            if (off[mid] <= it) cur = mid;
+            else hi = mid;
+        }
+        const uint32_t s = starts[cur], e = ends[cur];
+        const UnitDesc U = P.units[reg_unit[cur]];
+        const int64_t first = wq_peak_first(s, e);
+        const int64_t w_first = (first - 1) >> 6, w_last = ((int64_t)e - 1) >> 6;
+        const int64_t w0 = w_first + (int64_t)(it - off[cur]) * kProfWords;
+        const int nw = (int)i64min(kProfWords, w_last - w0 + 1);
+        const int64_t x_lo = 1 + 64 * w0;
+        gu8 *pl = POOL == 0 ? plane_u8(U, S, 0, P.nc[0]) : pooled_u8(U, S);
+        const WideScreen W = wide_stretch_screen(pl, (int64_t)(U.stride / 4), bw, x_lo, nw, pre, lane);
+        // (ALL: a word without a pooled tag in reach -- beside a control-only
+        // add -- is still a processed position, with the score 0.0)
+        double best = -__builtin_inf();
+        int64_t bx = -kWqNone;
+        wide_stretch_scores<POOL, true>(P, U, S, 0, bw, x_lo, nw, W, pre, cap, hcnt, hpos, lane,
+                                        [&](int64_t x, double f) {  // (ascending x per lane: the first maximum)
+                                            if (x >= first && x <= (int64_t)e && f > best) {
+                                                best = f;
+                                                bx = x;
+                                            }
+                                        });
+        const double m = wave_max_d(best);
+        const int64_t at = wq_wave_min(best == m ? bx : -kWqNone);
+        if (lane == 0) {
+            part_val[it] = m;
+            part_pos[it] = at == -kWqNone ? 0u : (uint32_t)at;
+        }
+    }
+}
+
+// each region's partials in stretch order -> its peak: the largest score, on
+// equal scores the lower position (positions ascend with the stretches, so
+// this is the first maximum whatever order the lanes meet them in).  One wave
+// per region.
+__global__ void __launch_bounds__(256) wide_peak_merge_kernel(const uint64_t *__restrict__ nreg_p, uint64_t reg_cap,
+                                                              const uint64_t *__restrict__ off,
+                                                              const double *__restrict__ part_val,
+                                                              const uint32_t *__restrict__ part_pos,
+                                                              uint64_t part_cap, uint32_t *peak_pos,
+                                                              double *peak_val) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint64_t n = *nreg_p < reg_cap ? *nreg_p : reg_cap;
+    for (uint64_t r = wave; r < n; r += nwaves) {
+        const uint64_t a = off[r], b = off[r + 1] < part_cap ? off[r + 1] : part_cap;
+        double best = -__builtin_inf();
+        uint32_t bx = 0xFFFFFFFFu;
+        for (uint64_t i = a + lane; i < b; i += 64) {
+            const double v = part_val[i];
+            const uint32_t p = part_pos[i];
+            if (v > best || (v == best && p < bx)) {
+                best = v;
+                bx = p;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ov = __shfl_xor(best, o);
+            const uint32_t op = (uint32_t)__shfl_xor((int)bx, o);
+            if (ov > best || (ov == best && op < bx)) {
+                best = ov;
+                bx = op;
+            }
+        }
+        if (lane == 0) {
+            peak_pos[r] = bx;
+            peak_val[r] = best;
+        }
     }
 }
 
