@@ -196,9 +196,13 @@ int up_reset_units(up_ctx *ctx);
  * parallel kernels (wide_runs_kernel, wide_peak_kernel), K2 / K3, the
  * placement and the head chains as for K1q, inside this blocking call only
  * (UNIPEAK_WIDE_Q11=0, read at up_open, keeps the replay for A/B runs).
+ * Nondirectional units take wide K1q under the same conditions once
+ * up_set_wide_q11_nd is on: peaks of forwardScore + reverseScore, the strand
+ * correlation of regions up to 65536 stored positions from wide_corr_kernel
+ * and of longer ones from wide_corr_stage_kernel / wide_corr_chain_kernel.
  * A negative coefficient at a threshold <= 0,
  * the -w capture with a head unit at a threshold <= 0, and bw > 511 at a
- * threshold <= 0 on nondirectional units or with the -w capture on, bw from
+ * threshold <= 0 on nondirectional units without up_set_wide_q11_nd or with the -w capture on, bw from
  * 32768 on, or nondirectional units above 511 with the -w
  * capture on run the exact
  * state machine over every unit instead (K0, as independent chains from
@@ -309,8 +313,9 @@ int up_last_stats_kind(up_ctx *ctx);
  * runs: the records do not depend on it. */
 int up_last_exact_kind(up_ctx *ctx);
 /* how the pass completed last found its regions: 0 K1 (K1a + K1b), 1 K1w
- * (bw above 511), 2 K1q (a threshold <= 0; above bw 511 its wide form on
- * directional units, up to 32767), 3 the exact replay of every unit
+ * (bw above 511), 2 K1q (a threshold <= 0; above bw 511 its wide form, up to
+ * 32767: on directional units, and on nondirectional ones with
+ * up_set_wide_q11_nd on), 3 the exact replay of every unit
  * (K0); -1 when no pass has completed or it had no units.  The K0 chains of
  * head units inside a K1 / K1w / K1q pass do not change the value.  For
  * tests and A/B runs: the records do not depend on it. */
@@ -323,8 +328,9 @@ int up_last_scan_kind(up_ctx *ctx);
 int up_scan_density(up_ctx *ctx, uint32_t *bytes_per_1024);
 /* device-side timings of the last up_run in ms: [0]=K1 scan, [1]=K2
  * segment, [2]=K3 stats (with wide_corr_kernel, the strand correlation of a
- * nondirectional K1w pass, or wide K1q's peak kernels, which run just before
- * K3; wide K1q's run kernel counts under [0]), [3]=whole up_run wall, [4]=K1 launches; with n > 5
+ * nondirectional K1w or wide K1q pass -- behind wide K1q with the stage and
+ * chain kernels of its long regions --, or wide K1q's peak kernels, which run
+ * just before K3; wide K1q's run kernel counts under [0]), [3]=whole up_run wall, [4]=K1 launches; with n > 5
  * also [5]=the dense-profile kernel of the last up_unit_profile* call (HIP
  * events around it); with n > 6 also [6]=K0 and [7]=the placement kernels of
  * the last pass that placed its head units itself (up_set_head_place) at
@@ -338,12 +344,13 @@ int up_timings(up_ctx *ctx, double *ms, int n);
  * fused profile path up to UP_MAX_PARALLEL_BW; wider kernels where K1w runs
  * (directional units, a threshold > 0, bw up to 32767): wide_profile_kernel,
  * every score the ascending sum K1w forms, out_r all zero; the same kernel
- * where wide K1q runs (directional units, a threshold <= 0, the -w capture
+ * where wide K1q runs (a threshold <= 0, the -w capture
  * off: it does not look at the threshold).  Nondirectional
  * units above UP_MAX_PARALLEL_BW: refused by default; with
- * up_set_wide_nd_full on, the kernel's two-strand form fills out_f with
- * forwardScore and out_r with reverseScore, each its own ascending sum (the
- * caller adds them; out_r = NULL is UP_E_ARG there).  Refused
+ * up_set_wide_nd_full on (a threshold > 0) or up_set_wide_q11_nd on (a
+ * threshold <= 0 where wide K1q runs), the kernel's two-strand form fills
+ * out_f with forwardScore and out_r with reverseScore, each its own ascending
+ * sum (the caller adds them; out_r = NULL is UP_E_ARG there).  Refused
  * (UP_E_UNSUPPORTED) wherever up_run takes the exact replay of every unit. */
 int up_unit_profile(up_ctx *ctx, uint32_t unit, double *out_f, double *out_r,
                     uint32_t len);
@@ -380,11 +387,31 @@ int up_unit_profile_range(up_ctx *ctx, uint32_t unit, uint64_t first, uint32_t c
  *    kernel, up_run_async admitted (each pass slot in flight then holds its own
  *    64 MB of strand-correlation slabs when the correlation is evaluated).
  * UP_E_STATE while a pass is in flight. UNIPEAK_WIDE_ND=0 still forces the
- * replay whatever this says; a threshold <= 0 (for nondirectional units: the
- * directional ones run wide K1q) and bw >= 32768 keep the replay
+ * replay whatever this says; a threshold <= 0 (up_set_wide_q11_nd below is
+ * the switch of that case) and bw >= 32768 keep the replay
  * and the refusals as well.  The records and the -w profile do not depend on
  * it; bin/regions sets it.  Making 1 the default is a later change. */
 int up_set_wide_nd_full(up_ctx *ctx, int on);
+/* nondirectional units above UP_MAX_PARALLEL_BW at a threshold <= 0 (bw
+ * 512..32767, the -w capture off, no coefficient below 0):
+ * 0 (default): the exact replay of every unit, up_unit_profile* refused.
+ * 1: wide K1q as on directional units, inside the blocking up_run only
+ *    (up_run_async stays refused; up_last_scan_kind 2): peaks of forwardScore +
+ *    reverseScore, the strand correlation (when it is evaluated) of regions
+ *    of more than 65536 stored positions staged by many waves and chained by
+ *    one through a staging area of at most 1 GiB; up_unit_profile* served by
+ *    the profile kernel's two-strand form; up_shift_scan / up_shift_best form
+ *    the regions' dense scores as behind K1w (2 * length doubles per region).
+ * UP_E_STATE while a pass is in flight.  UNIPEAK_WIDE_Q11_ND=0 (read at
+ * up_open, for A/B runs and tests) forces the replay whatever this says, as
+ * do UNIPEAK_WIDE_Q11=0 and UNIPEAK_WIDE=0; the -w capture, a negative
+ * coefficient and bw >= 32768 keep the replay and the refusals as well.
+ * UNIPEAK_WIDE_CORR_LONG=<positions> and UNIPEAK_WIDE_CORR_TILE=<positions>
+ * (read at up_open) override the long-region limit and the staging area's
+ * size: test-only, to reach round boundaries with small inputs.  The records
+ * do not depend on any of it; bin/regions -D and bin/strand_shift set the
+ * switch.  Making 1 the default is a later change. */
+int up_set_wide_q11_nd(up_ctx *ctx, int on);
 /* Head units (quirk Q1) replayed and merged on the device, inside the pass.
  * 0 (default): after a pass with head units up_run / up_run_wait run K0 on
  *    the context stream, copy its records and the pass's K1-K3 records to the

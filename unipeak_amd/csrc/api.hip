@@ -108,6 +108,19 @@ struct up_ctx {
     bool wide_nd = true;             // K1w for nondirectional units (UNIPEAK_WIDE_ND=0: the replay)
     bool wide_nd_full = false;       // those units' -w capture, dense profile and up_run_async (up_set_wide_nd_full)
     bool wide_q11 = true;            // wide K1q: threshold <= 0 at bw 512 .. 32,767 (UNIPEAK_WIDE_Q11=0: the replay)
+    bool wide_q11_nd = false;        // wide K1q for nondirectional units as well (up_set_wide_q11_nd)
+    bool wide_q11_nd_env = true;     // UNIPEAK_WIDE_Q11_ND=0: the replay for them whatever the switch says
+    // the strand correlation behind nondirectional wide K1q (wide.hip): regions of
+    // more than corr_long stored positions take the stage / chain kernels, whose
+    // staging area holds corr_tile positions (test-only overrides, read at up_open:
+    // UNIPEAK_WIDE_CORR_LONG, UNIPEAK_WIDE_CORR_TILE)
+    uint64_t corr_long = kCorrLong, corr_tile = kCorrTile;
+    // ... their state (K1q passes run one at a time, inside the blocking up_run):
+    // the two prefixes, the per-region carries, the staging area and the
+    // positions it holds; wide_peak_kernel<POOL, true>'s forward scores
+    DevBuf<uint64_t> d_wc_ioff, d_wc_aoff;
+    DevBuf<double> d_wc_carry, d_wc_stage, d_wq_fstash;
+    uint64_t wc_stage_cap = 0;
     bool use_graphs = true;          // passes as hipGraphs (UNIPEAK_GRAPHS=0: plain launches)
     // streams of the passes: every K1a on one high-priority stream (stream
     // order serialises them; as resources free up the dispatcher serves it
@@ -485,6 +498,9 @@ int up_open(int hip_device, up_ctx **out) {
     if (const char *e = getenv("UNIPEAK_K1B_ONE")) c->k1b_one = atoi(e) != 0;
     if (const char *e = getenv("UNIPEAK_WIDE_ND")) c->wide_nd = atoi(e) != 0;
     if (const char *e = getenv("UNIPEAK_WIDE_Q11")) c->wide_q11 = atoi(e) != 0;
+    if (const char *e = getenv("UNIPEAK_WIDE_Q11_ND")) c->wide_q11_nd_env = atoi(e) != 0;
+    if (const char *e = getenv("UNIPEAK_WIDE_CORR_LONG")) c->corr_long = std::max<uint64_t>(4, strtoull(e, nullptr, 10));
+    if (const char *e = getenv("UNIPEAK_WIDE_CORR_TILE")) c->corr_tile = std::max<uint64_t>(64, strtoull(e, nullptr, 10));
     if (const char *e = getenv("UNIPEAK_K1B_BLOCKS")) c->k1b_blocks = std::max(0, atoi(e));
     if (const char *e = getenv("UNIPEAK_CHAINS")) c->n_chain = std::min(4, std::max(1, atoi(e)));
     if (const char *e = getenv("UNIPEAK_LAUNCHER")) c->use_launcher = e[0] != '0';
@@ -1444,6 +1460,9 @@ static void dispatch_exact(up_ctx *c, hipStream_t st, const ScanParams &P, uint3
 // wide_corr_kernel's grid (one wave per workgroup, one global slab each):
 // four waves per CU
 static unsigned wide_corr_blocks(const up_ctx *c) { return 4u * (unsigned)(c->ncu > 0 ? c->ncu : 256); }
+// wide_peak_kernel<POOL, true>'s largest grid (a slab of forward scores per
+// workgroup): eight waves per CU
+static unsigned wide_peak_nd_blocks(const up_ctx *c) { return 8u * (unsigned)(c->ncu > 0 ? c->ncu : 256); }
 
 // the LDS hit lists of the dense wide scores; UNIPEAK_WIDE_PROFILE_LIST=0:
 // the direct window walk (A/B)
@@ -1613,16 +1632,21 @@ static bool wide_mode(const up_ctx *c) {
 static bool wide_nd_mode(const up_ctx *c) { return c->p.nondir && wide_mode(c); }
 
 // wide K1q (wide.hip): a threshold <= 0 with non-negative scores at kMaxBw <
-// bw <= kMaxWideBw on directional units, the -w capture off: wide_runs_kernel
-// finds the runs of processed positions, wide_peak_kernel their peaks, K2 / K3
-// / the placement and the K0 head chains follow as behind narrow K1q
-// (run_q11), so its passes too run only inside the blocking up_run.
-// Nondirectional units keep the replay: one region can span a contig and its
-// strand correlation is a sequential FP64 chain over every position.
-// UNIPEAK_WIDE_Q11=0 (read at up_open): the replay (A/B, tests).
+// bw <= kMaxWideBw, the -w capture off: wide_runs_kernel finds the runs of
+// processed positions (over every strand's tracks), wide_peak_kernel their
+// peaks, K2 / K3 / the placement and the K0 head chains follow as behind
+// narrow K1q (run_q11), so its passes too run only inside the blocking up_run.
+// Nondirectional units take it only with up_set_wide_q11_nd on (off by
+// default: the replay): their peaks are those of forwardScore + reverseScore
+// (wide_peak_kernel<POOL, true>), and one region can span a contig, so the
+// strand correlation of a region of more than corr_long stored positions is
+// staged by many waves and chained by one (launch_wide_corr_long).
+// UNIPEAK_WIDE_Q11=0 (read at up_open): the replay (A/B, tests);
+// UNIPEAK_WIDE_Q11_ND=0 (read at up_open): the replay for nondirectional
+// units whatever the switch says.
 static bool wide_q11_mode(const up_ctx *c) {
     return c->wide_q11 && wide_on() && q11_scores_ok(c) && c->p.bw > kMaxBw && c->p.bw <= kMaxWideBw &&
-           !c->p.nondir && !c->prof_capture;
+           (!c->p.nondir || (c->wide_q11_nd && c->wide_q11_nd_env)) && !c->prof_capture;
 }
 
 static bool replay_mode(const up_ctx *c) {
@@ -2324,6 +2348,41 @@ static int head_place_launch(up_ctx *c, int slot, hipStream_t st) {
     return UP_OK;
 }
 
+// strandCorr(0) of the regions of more than corr_long stored positions behind
+// nondirectional wide K1q (wide.hip: stage + chain).  The rounds are fixed on
+// the host from the context's positions, which bound the sum of the regions'
+// lengths; nothing is read back, a round past the real total exits at once.
+// One round: sweep 2 chains the scores sweep 1 staged.  More: every round of
+// sweep 2 stages its tile again (the kernel itself skips that when the real
+// total fits one tile after all).
+static int launch_wide_corr_long(up_ctx *c, up_ctx::Pass &ps, const ScanParams &SP, uint64_t cap) {
+    const uint64_t tile = c->corr_tile, scap = c->wc_stage_cap;
+    const uint64_t bound = (uint64_t)c->nstrips * kStrip;
+    const uint64_t rounds = std::max<uint64_t>(1, (bound + tile - 1) / tile);
+    const uint32_t lcap = wide_list_cap();
+    const size_t lds = prof_lds_bytes(c->p.bw);
+    const unsigned sblocks = (unsigned)std::min<uint64_t>(scap / (kProfWords * 64) + 2, 8192);
+    const unsigned cblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(cap, 1024));
+    hipStream_t st = ps.stream;
+    hipLaunchKernelGGL(wide_corr_prefix_kernel, dim3(1), dim3(1024), 0, st, ps.d_starts.p, ps.d_ends.p, ps.d_nreg.p,
+                       cap, c->corr_long, c->d_wc_ioff.p, c->d_wc_aoff.p);
+    for (int sweep = 1; sweep <= 2; ++sweep)
+        for (uint64_t k = 0; k < rounds; ++k) {
+            if (sweep == 1 || rounds > 1)
+                with_pool_mode(pool_mode(c), [&](auto pm) {
+                    hipLaunchKernelGGL(wide_corr_stage_kernel<decltype(pm)::value>, dim3(sblocks), dim3(64), lds, st,
+                                       SP, ps.d_starts.p, ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, cap,
+                                       c->d_wc_ioff.p, c->d_wc_aoff.p, tile, scap, k, sweep, lcap,
+                                       c->d_wc_stage.p);
+                });
+            hipLaunchKernelGGL(wide_corr_chain_kernel, dim3(cblocks), dim3(64), 0, st, ps.d_starts.p, ps.d_ends.p,
+                               ps.d_nreg.p, cap, c->d_wc_aoff.p, c->corr_long, tile, scap, k, sweep,
+                               c->d_wc_stage.p, c->d_wc_carry.p, ps.d_wcorr.p);
+        }
+    HIPCHK(hipGetLastError());
+    return UP_OK;
+}
+
 static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatParams &P, uint64_t cap,
                         uint32_t k1a_waves, uint32_t k1a_xcap, bool events) {
     up_ctx::Pass &ps = c->pass[slot];
@@ -2353,13 +2412,19 @@ static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatPar
                                            // reads as known peaks (timed with K3: up_timings [2])
         const uint32_t lcap = wide_list_cap();
         const size_t lds = prof_lds_bytes(c->p.bw);
-        const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ps.wq_cap, 8192));
+        const bool nd = c->p.nondir != 0;  // (up_set_wide_q11_nd: peaks of forwardScore + reverseScore)
+        const unsigned blocks =
+            (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ps.wq_cap, nd ? wide_peak_nd_blocks(c) : 8192));
+        double *fstash = nd ? c->d_wq_fstash.p : nullptr;
         hipLaunchKernelGGL(wide_peak_prefix_kernel, dim3(1), dim3(1024), 0, ps.stream, ps.d_starts.p, ps.d_ends.p,
                            ps.d_nreg.p, (uint64_t)cap, ps.d_wq_off.p);
-        with_pool_mode(pool_mode(c), [&](auto pm) {
-            hipLaunchKernelGGL(wide_peak_kernel<decltype(pm)::value>, dim3(blocks), dim3(64), lds, ps.stream, SP,
-                               ps.d_starts.p, ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, (uint64_t)cap,
-                               ps.d_wq_off.p, lcap, ps.d_wq_val.p, ps.d_wq_pos.p, ps.wq_cap);
+        with_flag(nd, [&](auto ndf) {
+            with_pool_mode(pool_mode(c), [&](auto pm) {
+                hipLaunchKernelGGL((wide_peak_kernel<decltype(pm)::value, decltype(ndf)::value>), dim3(blocks),
+                                   dim3(64), lds, ps.stream, SP, ps.d_starts.p, ps.d_ends.p, ps.d_runit.p,
+                                   ps.d_nreg.p, (uint64_t)cap, ps.d_wq_off.p, lcap, ps.d_wq_val.p, ps.d_wq_pos.p,
+                                   ps.wq_cap, fstash);
+            });
         });
         const unsigned mblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((cap + 3) / 4, 1024));
         hipLaunchKernelGGL(wide_peak_merge_kernel, dim3(mblocks), dim3(256), 0, ps.stream, ps.d_nreg.p,
@@ -2367,17 +2432,21 @@ static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatPar
                            ps.d_peak_val.p);
         HIPCHK(hipGetLastError());
     }
-    if (P.corr_in) {  // -D -y behind K1w: strandCorr(0) of every region (wide.hip), K3 takes it
-                      // (timed with K3: up_timings [2])
+    if (P.corr_in) {  // -D -y behind K1w or wide K1q: strandCorr(0) of every region (wide.hip), K3
+                      // takes it (timed with K3: up_timings [2])
         const unsigned blocks = wide_corr_blocks(c);
         const size_t lds = corr_lds_bytes(c->p.bw);
         const uint32_t lcap = wide_list_cap();
+        // (behind wide K1q a region can span a contig: the long ones go to launch_wide_corr_long)
+        const uint64_t long_n = ps.req_q11 ? c->corr_long : ~0ull;
         with_pool_mode(pool_mode(c), [&](auto pm) {
             hipLaunchKernelGGL(wide_corr_kernel<decltype(pm)::value>, dim3(blocks), dim3(64), lds, ps.stream, SP,
                                ps.d_starts.p, ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, (uint64_t)cap, ps.d_wslab.p,
-                               lcap, ps.d_wcorr.p);
+                               lcap, ps.d_wcorr.p, long_n);
         });
         HIPCHK(hipGetLastError());
+        if (ps.req_q11)
+            if (int r = launch_wide_corr_long(c, ps, SP, cap)) return r;
     }
     dispatch_stats(c, ps.stream, P, std::max<uint64_t>(ps.req_last_nreg, 1024));
     HIPCHK(hipGetLastError());
@@ -2439,6 +2508,16 @@ static int launch_pass(up_ctx *c, int slot) {
         HIPCHK(ps.d_wcorr.ensure(cap + 1));
         HIPCHK(ps.d_wslab.ensure((size_t)wide_corr_blocks(c) * 2 * kCorrSlab));
     }
+    if (wcorr && ps.req_q11) {  // the long regions' stage and chain kernels
+        // (the regions of a unit are disjoint: the strips' positions bound the axis)
+        c->wc_stage_cap = std::min<uint64_t>(c->corr_tile, (uint64_t)ns * kStrip);
+        HIPCHK(c->d_wc_ioff.ensure(cap + 2));
+        HIPCHK(c->d_wc_aoff.ensure(cap + 2));
+        HIPCHK(c->d_wc_carry.ensure(5 * (cap + 1)));
+        HIPCHK(c->d_wc_stage.ensure(2 * c->wc_stage_cap + 2));
+    }
+    if (ps.req_q11 && c->p.bw > kMaxBw && c->p.nondir)
+        HIPCHK(c->d_wq_fstash.ensure((size_t)wide_peak_nd_blocks(c) * kCorrSlab));
     if (ps.req_q11 && c->p.bw > kMaxBw) {
         // the regions of a unit are disjoint, so their stretches of 4,096
         // positions number at most positions / 4,096 + 2 per region: the area
@@ -3436,10 +3515,10 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
     }
     // global slab space only for regions whose scores do not stay in K4's
     // LDS: replayed ones (their stored scores are copied in) and long ones
-    // (the last pass ran K1w: K4's own KDE spans NH <= 8 window words, so
+    // (the last pass ran K1w or wide K1q: K4's own KDE spans NH <= 8 window words, so
     // wide_fill_kernel forms the scores of its regions into the slab first --
     // mark 2; head-replayed regions keep their stored scores)
-    const bool wide = c->last_scan_kind == 1;
+    const bool wide = c->last_scan_kind == 1 || (c->last_scan_kind == 2 && c->p.bw > kMaxBw);  // (nondirectional: checked above)
     bool any_fill = false;
     std::vector<uint64_t> off(n, 0);
     std::vector<uint8_t> pref(n + 1, 0);
@@ -3530,7 +3609,8 @@ int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t cou
     if (r) return r;
     if (busy(c)) return UP_E_STATE;  // a pass in flight reads this state
     if (unit >= c->units.size() || !out_f || first < 1 || count == 0) return UP_E_ARG;
-    if (!out_r && wide_nd_mode(c)) return UP_E_ARG;  // both strands' scores are the answer
+    // both strands' scores are the answer (K1w, or wide K1q behind up_set_wide_q11_nd)
+    if (!out_r && c->p.nondir && c->p.bw > kMaxBw) return UP_E_ARG;
     HIPCHK(hipSetDevice(c->dev));
     if ((r = sync_units(c))) return r;
     const Unit &u = c->units[unit];
@@ -3552,7 +3632,8 @@ int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t cou
         const uint64_t nstretch = ((first + count - 2) / 64 - (first - 1) / 64) / kProfWords + 1;
         const dim3 grid((unsigned)std::min<uint64_t>(nstretch, 1u << 16));
         const size_t lds = prof_lds_bytes(c->p.bw);
-        // (nondirectional: f and r, each its own ascending sum -- up_set_wide_nd_full: check_runnable)
+        // (nondirectional: f and r, each its own ascending sum -- up_set_wide_nd_full or
+        // up_set_wide_q11_nd: check_runnable)
         with_flag(c->p.nondir != 0, [&](auto nd) {
             with_pool_mode(pool_mode(c), [&](auto pm) {
                 hipLaunchKernelGGL((wide_profile_kernel<decltype(pm)::value, decltype(nd)::value>), grid, dim3(64),
@@ -3626,6 +3707,13 @@ int up_set_wide_nd_full(up_ctx *c, int on) {
     if (!c) return UP_E_ARG;
     if (busy(c)) return UP_E_STATE;
     c->wide_nd_full = on != 0;
+    return UP_OK;
+}
+
+int up_set_wide_q11_nd(up_ctx *c, int on) {
+    if (!c) return UP_E_ARG;
+    if (busy(c)) return UP_E_STATE;
+    c->wide_q11_nd = on != 0;
     return UP_OK;
 }
 

@@ -34,8 +34,12 @@
 //    pass, between K2 and K3 (K3's own KDE spans NH <= 8 window words);
 //  * wide_fill_kernel: the (f, r) slabs of requested regions for K4
 //    (up_shift_scan, up_shift_best);
-//  * wide_peak_kernel: the peaks of wide K1q's regions -- a threshold <= 0 on
-//    directional units, whose runs wide_runs_kernel finds (end of this file).
+//  * wide_peak_kernel: the peaks of wide K1q's regions -- a threshold <= 0,
+//    whose runs wide_runs_kernel finds; on nondirectional units
+//    (up_set_wide_q11_nd) the peaks of forwardScore + reverseScore;
+//  * wide_corr_stage_kernel: both strands' scores of the long regions of such
+//    a nondirectional pass, which wide_corr_chain_kernel sums in position
+//    order (end of this file).
 
 namespace upk {
 
@@ -449,10 +453,14 @@ __device__ __forceinline__ void wide_range_scores(const ScanParams &P, const Uni
 // Memory: one slab of kCorrSlab (f, r) positions per wave, whatever the
 // regions hold; a region that fits keeps its scores for the second pass, a
 // longer one forms them again slab by slab (the same sums, so the same bits).
+// Regions of more than long_n stored positions are left out (behind wide K1q
+// the stage and chain kernels at the end of this file take them; K1w passes
+// ~0: every region).
 template <int POOL>
 __global__ void __launch_bounds__(64) wide_corr_kernel(ScanParams P, const uint32_t *starts, const uint32_t *ends,
                                                        const uint32_t *reg_unit, const uint64_t *nreg_p,
-                                                       uint64_t reg_cap, double *slabs, uint32_t cap, double *out) {
+                                                       uint64_t reg_cap, double *slabs, uint32_t cap, double *out,
+                                                       uint64_t long_n) {
     extern __shared__ __attribute__((aligned(16))) unsigned char corr_lds[];
     const WideLds L = wide_lds(corr_lds);
     const int lane = threadIdx.x;
@@ -464,6 +472,7 @@ __global__ void __launch_bounds__(64) wide_corr_kernel(ScanParams P, const uint3
         const uint32_t left = starts[ri], right = ends[ri];
         const UnitDesc U = P.units[reg_unit[ri]];
         const uint32_t n = right - left + 1;
+        if (n > long_n) continue;  // (wave-uniform) the stage and chain kernels' region
         double corr = __builtin_nan("");
         if (n > 3) {
             const bool one = n <= (uint32_t)kCorrSlab;  // the slab keeps the whole region
@@ -765,13 +774,19 @@ __global__ void __launch_bounds__(1024) wide_peak_prefix_kernel(const uint32_t *
 // Every score is the wide_stretch_scores ascending sum; the wave reduces its
 // stretch to (largest score, lowest position holding it) -> part_val /
 // part_pos[it].  No floating-point atomics.
-template <int POOL>
+// NONDIR: the score of a position is forwardScore + reverseScore, each its own
+// ascending sum and one FP64 add as in Region::addPos: the forward walk parks
+// the stretch's scores in the workgroup's slab of fstash (kCorrSlab doubles per
+// workgroup; every lane reads back only what it wrote), the reverse walk adds
+// and reduces.  The screen is the pooled plane, which holds both strands' tags.
+template <int POOL, bool NONDIR>
 __global__ void __launch_bounds__(64) wide_peak_kernel(ScanParams P, const uint32_t *__restrict__ starts,
                                                        const uint32_t *__restrict__ ends,
                                                        const uint32_t *__restrict__ reg_unit,
                                                        const uint64_t *__restrict__ nreg_p, uint64_t reg_cap,
                                                        const uint64_t *__restrict__ off, uint32_t cap,
-                                                       double *part_val, uint32_t *part_pos, uint64_t part_cap) {
+                                                       double *part_val, uint32_t *part_pos, uint64_t part_cap,
+                                                       double *fstash) {
     extern __shared__ __attribute__((aligned(16))) unsigned char prof_lds[];
     double *hcnt = (double *)prof_lds;
     uint32_t *hpos = (uint32_t *)(prof_lds + (size_t)kProfHits * 8);
@@ -796,19 +811,28 @@ __global__ void __launch_bounds__(64) wide_peak_kernel(ScanParams P, const uint3
         const int64_t w0 = w_first + (int64_t)(it - off[cur]) * kProfWords;
         const int nw = (int)i64min(kProfWords, w_last - w0 + 1);
         const int64_t x_lo = 1 + 64 * w0;
-        gu8 *pl = POOL == 0 ? plane_u8(U, S, 0, P.nc[0]) : pooled_u8(U, S);
+        gu8 *pl = (POOL == 0 && !NONDIR) ? plane_u8(U, S, 0, P.nc[0]) : pooled_u8(U, S);
         const WideScreen W = wide_stretch_screen(pl, (int64_t)(U.stride / 4), bw, x_lo, nw, pre, lane);
         // (ALL: a word without a pooled tag in reach -- beside a control-only
         // add -- is still a processed position, with the score 0.0)
         double best = -__builtin_inf();
         int64_t bx = -kWqNone;
-        wide_stretch_scores<POOL, true>(P, U, S, 0, bw, x_lo, nw, W, pre, cap, hcnt, hpos, lane,
-                                        [&](int64_t x, double f) {  // (ascending x per lane: the first maximum)
-                                            if (x >= first && x <= (int64_t)e && f > best) {
-                                                best = f;
-                                                bx = x;
-                                            }
-                                        });
+        auto take = [&](int64_t x, double f) {  // (ascending x per lane: the first maximum)
+            if (x >= first && x <= (int64_t)e && f > best) {
+                best = f;
+                bx = x;
+            }
+        };
+        if constexpr (!NONDIR) {
+            wide_stretch_scores<POOL, true>(P, U, S, 0, bw, x_lo, nw, W, pre, cap, hcnt, hpos, lane, take);
+        } else {
+            double *fs = fstash + (uint64_t)blockIdx.x * kCorrSlab;
+            wide_stretch_scores<POOL, true>(P, U, S, 0, bw, x_lo, nw, W, pre, cap, hcnt, hpos, lane,
+                                            [&](int64_t x, double f) { fs[x - x_lo] = f; });
+            __syncthreads();  // the forward walk has read the list the reverse gather refills
+            wide_stretch_scores<POOL, true>(P, U, S, 1, bw, x_lo, nw, W, pre, cap, hcnt, hpos, lane,
+                                            [&](int64_t x, double r) { take(x, fs[x - x_lo] + r); });
+        }
         const double m = wave_max_d(best);
         const int64_t at = wq_wave_min(best == m ? bx : -kWqNone);
         if (lane == 0) {
@@ -856,6 +880,285 @@ __global__ void __launch_bounds__(256) wide_peak_merge_kernel(const uint64_t *__
         if (lane == 0) {
             peak_pos[r] = bx;
             peak_val[r] = best;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------
+// strandCorr(0) of the long regions of a nondirectional wide K1q pass.  A run
+// of processed positions can span a contig, and wide_corr_kernel would hand
+// all of it to one wave: both the dense scores (the expensive part) and the
+// five sequential FP64 sums (which cannot be split and stay bit-exact).  So a
+// region of more than kCorrLong stored positions s .. e (the reported left and
+// right are one higher; the peak range is s + 1 .. e) splits the two:
+//   wide_corr_prefix_kernel  per region its stretches and its stored positions
+//                            if it is long, else 0 -> two exclusive prefixes:
+//                            the items of the stage kernel and one cumulative
+//                            position axis that lays the long regions end to end
+//   wide_corr_stage_kernel   one wave per (long region, stretch): f and r of
+//                            the stretch's stored positions -- the
+//                            wide_stretch_scores sums wide_range_scores forms,
+//                            so the same bits -- into the staging area, 16 bytes
+//                            per position, at the position's place on the axis
+//   wide_corr_chain_kernel   one wave per long region: the staged scores in
+//                            position order with exactly wide_corr_kernel's
+//                            arithmetic -- sweep 1 carries the sums of f and r,
+//                            sweep 2 those of d1*d1, d2*d2 and d1*d2 -- then
+//                            sqrt(ss / (n - 1)) and the correlation into out[ri]
+// The staging area holds `tile` positions (kCorrTile).  Round k of a sweep
+// covers [k * tile, (k + 1) * tile) of the axis; a region cut by a round
+// boundary keeps its five sums in carry[5 ri ..] between rounds.  The host
+// enqueues a fixed number of rounds from the context's positions (which bound
+// the axis); a round past the axis' end exits at once, and when the whole
+// axis fits one round, sweep 2 finds sweep 1's scores still staged and the
+// stage kernel of sweep 2 exits at once as well.  The kernels are ordered by
+// the pass stream alone: no wave waits for another.
+constexpr uint64_t kCorrLong = 16ull * kCorrSlab;  // stored positions wide_corr_kernel still takes: 65,536
+constexpr uint64_t kCorrTile = 64ull << 20;        // positions of the staging area: 1 GiB
+
+__device__ __forceinline__ uint64_t wc_stretches(uint32_t s, uint32_t e) {
+    return (uint64_t)(((((int64_t)e - 1) >> 6) - (((int64_t)s - 1) >> 6)) / kProfWords + 1);
+}
+
+// the last i in [0, n) with off[i] <= v (off ascending, off[0] = 0 <= v < off[n]):
+// a region without items / positions shares its offset with the next one, so
+// this is the region that owns item / axis position v
+__device__ __forceinline__ uint64_t wc_owner(const uint64_t *__restrict__ off, uint64_t n, uint64_t v, uint64_t lo) {
+    uint64_t hi = n;
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (off[mid] <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// One block of 1,024 (wide_peak_prefix_kernel's scheme, two sums at once).
+__global__ void __launch_bounds__(1024) wide_corr_prefix_kernel(const uint32_t *__restrict__ starts,
+                                                                const uint32_t *__restrict__ ends,
+                                                                const uint64_t *__restrict__ nreg_p,
+                                                                uint64_t reg_cap, uint64_t long_n, uint64_t *ioff,
+                                                                uint64_t *aoff) {
+    __shared__ uint64_t sh[16];
+    __shared__ uint64_t tot[2];
+    const uint64_t n = *nreg_p < reg_cap ? *nreg_p : reg_cap;
+    uint64_t ibase = 0, abase = 0;
+    for (uint64_t c0 = 0; c0 < n; c0 += 1024) {
+        const uint64_t i = c0 + threadIdx.x;
+        uint64_t items = 0, len = 0;
+        if (i < n) {
+            const uint32_t s = starts[i], e = ends[i];
+            const uint64_t m = (uint64_t)e - s + 1;
+            if (m > long_n) {
+                items = wc_stretches(s, e);
+                len = m;
+            }
+        }
+        const uint64_t iinc = block_incl_sum(items, sh);
+        const uint64_t ainc = block_incl_sum(len, sh);
+        if (i < n) {
+            ioff[i] = ibase + iinc - items;
+            aoff[i] = abase + ainc - len;
+        }
+        if (threadIdx.x == 1023) {
+            tot[0] = iinc;
+            tot[1] = ainc;
+        }
+        __syncthreads();
+        ibase += tot[0];
+        abase += tot[1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        ioff[n] = ibase;
+        aoff[n] = abase;
+    }
+}
+
+// stage: [f, r] of axis position A at stage[2 (A - round * tile)], A inside the
+// round and the area (stage_cap positions)
+template <int POOL>
+__global__ void __launch_bounds__(64) wide_corr_stage_kernel(ScanParams P, const uint32_t *__restrict__ starts,
+                                                             const uint32_t *__restrict__ ends,
+                                                             const uint32_t *__restrict__ reg_unit,
+                                                             const uint64_t *__restrict__ nreg_p, uint64_t reg_cap,
+                                                             const uint64_t *__restrict__ ioff,
+                                                             const uint64_t *__restrict__ aoff, uint64_t tile,
+                                                             uint64_t stage_cap, uint64_t round, int sweep,
+                                                             uint32_t cap, double *stage) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char prof_lds[];
+    double *hcnt = (double *)prof_lds;
+    uint32_t *hpos = (uint32_t *)(prof_lds + (size_t)kProfHits * 8);
+    uint32_t *pre = hpos + kProfHits;
+    const int lane = threadIdx.x;
+    const int bw = P.bw;
+    const int S = P.S;
+    const uint64_t n = *nreg_p < reg_cap ? *nreg_p : reg_cap;
+    const uint64_t total = aoff[n];
+    const uint64_t A0 = round * tile;
+    if (A0 >= total) return;                   // a round past the axis' end
+    if (sweep == 2 && total <= tile) return;   // one round holds everything: sweep 1's scores are still staged
+    const uint64_t A1 = A0 + tile < total ? A0 + tile : total;
+    // the items that hold the round's first and last position
+    uint64_t it_lo, it_hi;
+    {
+        const uint64_t r0 = wc_owner(aoff, n, A0, 0), r1 = wc_owner(aoff, n, A1 - 1, r0);
+        const int64_t x0 = (int64_t)starts[r0] + (int64_t)(A0 - aoff[r0]);
+        const int64_t x1 = (int64_t)starts[r1] + (int64_t)(A1 - 1 - aoff[r1]);
+        it_lo = ioff[r0] + (uint64_t)((((x0 - 1) >> 6) - (((int64_t)starts[r0] - 1) >> 6)) / kProfWords);
+        it_hi = ioff[r1] + (uint64_t)((((x1 - 1) >> 6) - (((int64_t)starts[r1] - 1) >> 6)) / kProfWords);
+    }
+    uint64_t cur = 0;
+    for (uint64_t it = it_lo + blockIdx.x; it <= it_hi; it += gridDim.x) {
+        cur = wc_owner(ioff, n, it, cur);
+        const uint32_t s = starts[cur], e = ends[cur];
+        const UnitDesc U = P.units[reg_unit[cur]];
+        const uint64_t a0 = aoff[cur];
+        const int64_t w_first = ((int64_t)s - 1) >> 6, w_last = ((int64_t)e - 1) >> 6;
+        const int64_t w0 = w_first + (int64_t)(it - ioff[cur]) * kProfWords;
+        const int nw = (int)i64min(kProfWords, w_last - w0 + 1);
+        const int64_t x_lo = 1 + 64 * w0;
+        const WideScreen W = wide_stretch_screen(pooled_u8(U, S), (int64_t)(U.stride / 4), bw, x_lo, nw, pre, lane);
+        auto put = [&](int64_t x, double v, int strand) {
+            if (x < (int64_t)s || x > (int64_t)e) return;
+            const uint64_t A = a0 + (uint64_t)(x - (int64_t)s);
+            if (A >= A0 && A < A1 && A - A0 < stage_cap) stage[2 * (A - A0) + strand] = v;
+        };
+        wide_stretch_scores<POOL, true>(P, U, S, 0, bw, x_lo, nw, W, pre, cap, hcnt, hpos, lane,
+                                        [&](int64_t x, double f) { put(x, f, 0); });
+        __syncthreads();  // the forward walk has read the list the reverse gather refills
+        wide_stretch_scores<POOL, true>(P, U, S, 1, bw, x_lo, nw, W, pre, cap, hcnt, hpos, lane,
+                                        [&](int64_t x, double r) { put(x, r, 1); });
+        __syncthreads();
+    }
+}
+
+// chain: the piece of every long region inside the round, one wave per region;
+// carry[5 ri + 0 .. 4] = sf, sr, ss1, ss2, ssr of region ri so far.
+// The wave takes kChainBlk words of 64 staged positions at a time, lane l the
+// l-th position of each word (one 16-byte load per word, the next block's
+// issued before this block's sums), forms its position's terms and hands them
+// round lane by lane through v_readlane: every lane then adds them in
+// position order, so each sum is the one sequential chain -- no LDS round
+// trip between two dependent adds (a first version read the terms back from
+// LDS one position at a time and spent ~50 ns per position waiting for it).
+constexpr int kChainBlk = 4;
+
+struct WcPair {
+    double f, r;
+};
+
+// the staged pairs of positions j0 + 64 c + lane (c < kChainBlk) below hi
+__device__ __forceinline__ void wc_load(WcPair (&v)[kChainBlk], const double *__restrict__ stage, uint64_t j0,
+                                        uint64_t hi, uint64_t A0, uint64_t stage_cap, int lane) {
+#pragma unroll
+    for (int c = 0; c < kChainBlk; ++c) {
+        const uint64_t j = j0 + 64 * (uint64_t)c + lane, q = j - A0;
+        v[c].f = 0.0;
+        v[c].r = 0.0;
+        if (j < hi && q < stage_cap) {
+            const double2 t = ((const double2 *)stage)[q];
+            v[c].f = t.x;
+            v[c].r = t.y;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64) wide_corr_chain_kernel(const uint32_t *__restrict__ starts,
+                                                             const uint32_t *__restrict__ ends,
+                                                             const uint64_t *__restrict__ nreg_p, uint64_t reg_cap,
+                                                             const uint64_t *__restrict__ aoff, uint64_t long_n,
+                                                             uint64_t tile, uint64_t stage_cap, uint64_t round,
+                                                             int sweep, const double *__restrict__ stage,
+                                                             double *carry, double *out) {
+    const int lane = threadIdx.x;
+    const uint64_t nreg = *nreg_p < reg_cap ? *nreg_p : reg_cap;
+    const uint64_t total = aoff[nreg];
+    const uint64_t A0 = round * tile;
+    if (A0 >= total) return;
+    const uint64_t A1 = A0 + tile < total ? A0 + tile : total;
+    constexpr uint64_t kBlk = 64ull * kChainBlk;
+    for (uint64_t ri = blockIdx.x; ri < nreg; ri += gridDim.x) {
+        const uint32_t left = starts[ri], right = ends[ri];
+        const uint64_t n = (uint64_t)right - left + 1;
+        const uint64_t a0 = aoff[ri], a1 = a0 + n;
+        if (n <= long_n || a0 >= A1 || a1 <= A0) continue;  // (wave-uniform)
+        const uint64_t lo = a0 > A0 ? a0 : A0, hi = a1 < A1 ? a1 : A1;
+        const bool fresh = a0 >= A0;  // the region begins in this round
+        double *cr = carry + 5 * ri;
+        WcPair cur[kChainBlk], nxt[kChainBlk];
+        wc_load(cur, stage, lo, hi, A0, stage_cap, lane);
+        if (sweep == 1) {
+            double sf = fresh ? 0.0 : cr[0], sr = fresh ? 0.0 : cr[1];
+            for (uint64_t j0 = lo; j0 < hi; j0 += kBlk) {
+                wc_load(nxt, stage, j0 + kBlk, hi, A0, stage_cap, lane);
+#pragma unroll
+                for (int c = 0; c < kChainBlk; ++c) {
+                    const uint64_t base = j0 + 64 * (uint64_t)c;
+                    if (base + 64 <= hi) {
+#pragma unroll
+                        for (int l = 0; l < 64; ++l) {
+                            sf = sf + rl_d(cur[c].f, l);
+                            sr = sr + rl_d(cur[c].r, l);
+                        }
+                    } else if (base < hi) {
+                        const int nvalid = (int)(hi - base);
+                        for (int l = 0; l < nvalid; ++l) {
+                            sf = sf + rl_d(cur[c].f, l);
+                            sr = sr + rl_d(cur[c].r, l);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < kChainBlk; ++c) cur[c] = nxt[c];
+            }
+            if (lane == 0) {
+                cr[0] = sf;
+                cr[1] = sr;
+            }
+        } else {
+            const double m1 = cr[0] / (double)n, m2 = cr[1] / (double)n;
+            double ss1 = fresh ? 0.0 : cr[2], ss2 = fresh ? 0.0 : cr[3], ssr = fresh ? 0.0 : cr[4];
+            for (uint64_t j0 = lo; j0 < hi; j0 += kBlk) {
+                wc_load(nxt, stage, j0 + kBlk, hi, A0, stage_cap, lane);
+#pragma unroll
+                for (int c = 0; c < kChainBlk; ++c) {
+                    const uint64_t base = j0 + 64 * (uint64_t)c;
+                    const double d1 = cur[c].f - m1, d2 = cur[c].r - m2;
+                    const double p1 = d1 * d1, p2 = d2 * d2, p3 = d1 * d2;
+                    if (base + 64 <= hi) {
+#pragma unroll
+                        for (int l = 0; l < 64; ++l) {
+                            ss1 = ss1 + rl_d(p1, l);
+                            ss2 = ss2 + rl_d(p2, l);
+                            ssr = ssr + rl_d(p3, l);
+                        }
+                    } else if (base < hi) {
+                        const int nvalid = (int)(hi - base);
+                        for (int l = 0; l < nvalid; ++l) {
+                            ss1 = ss1 + rl_d(p1, l);
+                            ss2 = ss2 + rl_d(p2, l);
+                            ssr = ssr + rl_d(p3, l);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < kChainBlk; ++c) cur[c] = nxt[c];
+            }
+            if (lane == 0) {
+                cr[2] = ss1;
+                cr[3] = ss2;
+                cr[4] = ssr;
+            }
+            if (a1 <= A1) {  // the region ends in this round
+                double corr = __builtin_nan("");
+                if (n > 3) {
+                    const double sd1 = sqrt(ss1 / ((double)n - 1));
+                    const double sd2 = sqrt(ss2 / ((double)n - 1));
+                    corr = ssr / (((double)n - 1) * sd1 * sd2);
+                }
+                if (lane == 0) out[ri] = corr;
+            }
         }
     }
 }

@@ -415,6 +415,8 @@ void run_units(const EngineParams &ep, PassResult &out) {
         if (ep.profile && (rc = up_set_profile_capture(job.ctx, 1))) return fail(rc, "up_set_profile_capture");
         // (-D above bw 511: K1w and the profile kernel with the capture on, not the whole-buffer replay)
         if ((rc = up_set_wide_nd_full(job.ctx, 1))) return fail(rc, "up_set_wide_nd_full");
+        // (-D above bw 511 at -r <= 0: wide K1q, not the segmented replay)
+        if ((rc = up_set_wide_q11_nd(job.ctx, 1))) return fail(rc, "up_set_wide_q11_nd");
         // (head units of a -s run: replayed and merged on the device, inside the pass)
         if ((rc = up_set_head_place(job.ctx, 1))) return fail(rc, "up_set_head_place");
         std::vector<uint32_t> tp, tc;
