@@ -93,6 +93,21 @@ int64_t orc_run_unit(const double *kernel, uint32_t kernel_size,
                      const uint32_t *counts_fwd, const uint32_t *counts_rev,
                      orc_unit_region *out, uint32_t *out_sums, size_t cap);
 
+/* orc_run_unit plus, for every candidate region (accepted or rejected, in
+ * emission order, the first cap of them), Region::strandCorr(shift) for shift
+ * = 0 .. max_shift (misc/data.cpp:184-193; src/strand_shift.cpp:211-212)
+ * over the scores the state machine stored in the region:
+ * tab[k * (max_shift + 1) + shift], cap x (max_shift + 1) doubles. */
+int64_t orc_run_unit_shifts(const double *kernel, uint32_t kernel_size,
+                            double region_thr, double kurt_thr, double corr_thr,
+                            double hit_thr, int buffer_forward, int nondir,
+                            uint16_t n_expt, const uint8_t *control,
+                            const double *coeffs, uint32_t n_coeffs,
+                            uint32_t contig, size_t n, const uint32_t *pos,
+                            const uint32_t *counts_fwd, const uint32_t *counts_rev,
+                            orc_unit_region *out, uint32_t *out_sums, size_t cap,
+                            uint16_t max_shift, double *tab);
+
 /* dense profile of one unit (f and r for positions 1..len) -- computed by
  * running the state machine with a profile sink; positions never processed
  * stay 0. */

@@ -425,6 +425,8 @@ typedef struct {
     uint32_t *sums;
     size_t cap, n;
     uint16_t n_expt;
+    double *tab; /* optional: strandCorr(0 .. max_shift) per candidate */
+    uint16_t max_shift;
 } unit_sink;
 
 static void fill_unit_region(unit_sink *u, orc_region *g, int accepted) {
@@ -442,6 +444,11 @@ static void fill_unit_region(unit_sink *u, orc_region *g, int accepted) {
         o->kurtosis = g->n ? orc_region_kurtosis(g) : NAN;
         o->corr = orc_region_corr(g, 0);
         if (u->sums) orc_region_expt_sums(g, u->sums + u->n * u->n_expt);
+        /* strand_shift.cpp:211-212: strandCorr(shift), shifts ascending */
+        if (u->tab)
+            for (uint32_t s = 0; s <= u->max_shift; ++s)
+                u->tab[u->n * ((size_t)u->max_shift + 1) + s] =
+                    orc_region_corr(g, (uint16_t)s);
     }
     u->n++;
 }
@@ -458,15 +465,16 @@ static void unit_rej_cb(void *user, orc_region *g) {
 
 void orc_buf_set_reject_cb(orc_buf *b, orc_region_cb cb) { b->rej_cb = cb; }
 
-int64_t orc_run_unit(const double *kernel, uint32_t kernel_size,
-                     double region_thr, double kurt_thr, double corr_thr,
-                     double hit_thr, int buffer_forward, int nondir,
-                     uint16_t n_expt, const uint8_t *control,
-                     const double *coeffs, uint32_t n_coeffs,
-                     uint32_t contig, size_t n, const uint32_t *pos,
-                     const uint32_t *counts_fwd, const uint32_t *counts_rev,
-                     orc_unit_region *out, uint32_t *out_sums, size_t cap) {
-    unit_sink u = {out, out_sums, cap, 0, n_expt};
+static int64_t run_unit(const double *kernel, uint32_t kernel_size,
+                        double region_thr, double kurt_thr, double corr_thr,
+                        double hit_thr, int buffer_forward, int nondir,
+                        uint16_t n_expt, const uint8_t *control,
+                        const double *coeffs, uint32_t n_coeffs,
+                        uint32_t contig, size_t n, const uint32_t *pos,
+                        const uint32_t *counts_fwd, const uint32_t *counts_rev,
+                        orc_unit_region *out, uint32_t *out_sums, size_t cap,
+                        uint16_t max_shift, double *tab) {
+    unit_sink u = {out, out_sums, cap, 0, n_expt, tab, max_shift};
     orc_buf *b = orc_buf_new(kernel, kernel_size, region_thr, kurt_thr,
                              corr_thr, hit_thr, buffer_forward, n_expt, control,
                              coeffs, n_coeffs, unit_cb, &u, NULL, NULL);
@@ -495,6 +503,38 @@ int64_t orc_run_unit(const double *kernel, uint32_t kernel_size,
     orc_buf_flush(b);
     orc_buf_free(b);
     return (int64_t)u.n;
+}
+
+int64_t orc_run_unit(const double *kernel, uint32_t kernel_size,
+                     double region_thr, double kurt_thr, double corr_thr,
+                     double hit_thr, int buffer_forward, int nondir,
+                     uint16_t n_expt, const uint8_t *control,
+                     const double *coeffs, uint32_t n_coeffs,
+                     uint32_t contig, size_t n, const uint32_t *pos,
+                     const uint32_t *counts_fwd, const uint32_t *counts_rev,
+                     orc_unit_region *out, uint32_t *out_sums, size_t cap) {
+    return run_unit(kernel, kernel_size, region_thr, kurt_thr, corr_thr, hit_thr,
+                    buffer_forward, nondir, n_expt, control, coeffs, n_coeffs,
+                    contig, n, pos, counts_fwd, counts_rev, out, out_sums, cap,
+                    0, NULL);
+}
+
+/* orc_run_unit plus Region::strandCorr(0 .. max_shift) of every candidate
+ * (data.cpp:184-193, as strand_shift.cpp:211-212 calls it) over the scores
+ * the state machine stored in the region */
+int64_t orc_run_unit_shifts(const double *kernel, uint32_t kernel_size,
+                            double region_thr, double kurt_thr, double corr_thr,
+                            double hit_thr, int buffer_forward, int nondir,
+                            uint16_t n_expt, const uint8_t *control,
+                            const double *coeffs, uint32_t n_coeffs,
+                            uint32_t contig, size_t n, const uint32_t *pos,
+                            const uint32_t *counts_fwd, const uint32_t *counts_rev,
+                            orc_unit_region *out, uint32_t *out_sums, size_t cap,
+                            uint16_t max_shift, double *tab) {
+    return run_unit(kernel, kernel_size, region_thr, kurt_thr, corr_thr, hit_thr,
+                    buffer_forward, nondir, n_expt, control, coeffs, n_coeffs,
+                    contig, n, pos, counts_fwd, counts_rev, out, out_sums, cap,
+                    max_shift, tab);
 }
 
 /* a synthetic unit generated and run inside the oracle (bench.py's genome
@@ -527,7 +567,7 @@ int64_t orc_genome_unit(const double *kernel, uint32_t kernel_size, double regio
             for (size_t i = 0; i < tn[t]; ++i) bits[tp[t][i] >> 6] |= 1ull << (tp[t][i] & 63);
         }
     }
-    unit_sink u = {out, out_sums, cap, 0, n_expt};
+    unit_sink u = {out, out_sums, cap, 0, n_expt, NULL, 0};
     orc_buf *b = orc_buf_new(kernel, kernel_size, region_thr, kurt_thr, corr_thr, hit_thr,
                              buffer_forward, n_expt, control, NULL, 0, unit_cb, &u, NULL, NULL);
     b->rej_cb = unit_rej_cb;

@@ -71,10 +71,8 @@ class Oracle:
     def _opt(a, dt):
         return None if a is None else np.ascontiguousarray(a, dt)
 
-    def run_unit(self, bw, background, pos, counts_fwd, counts_rev=None, *, region_thr=25.0,
-                 kurt_thr=50.0, corr_thr=-1.0, hit_thr=10.0, buffer_forward=True,
-                 nondir=False, control=None, coeffs=None, contig=0, cap=1 << 16):
-        """All candidate regions (accepted and rejected) of one unit."""
+    def _run_unit(self, fn, extra, bw, background, pos, counts_fwd, counts_rev, region_thr, kurt_thr,
+                  corr_thr, hit_thr, buffer_forward, nondir, control, coeffs, contig, cap):
         k = self.kernel(bw, 1.0 / background)
         pos = np.ascontiguousarray(pos, np.uint32)
         S = counts_fwd.shape[1] if counts_fwd is not None else counts_rev.shape[1]
@@ -84,15 +82,45 @@ class Oracle:
         co = self._opt(coeffs, np.float64)
         out = np.zeros(cap, UNIT_DTYPE)
         sums = np.zeros((cap, S), np.uint32)
-        n = self.L.orc_run_unit(k.ctypes.data, k.size, region_thr, kurt_thr, corr_thr, hit_thr,
-                                int(buffer_forward), int(nondir), S, ctl.ctypes.data,
-                                None if co is None else co.ctypes.data,
-                                0 if co is None else co.size, contig, pos.size, pos.ctypes.data,
-                                None if cf is None else cf.ctypes.data,
-                                None if cr is None else cr.ctypes.data,
-                                out.ctypes.data, sums.ctypes.data, cap)
+        n = fn(k.ctypes.data, k.size, region_thr, kurt_thr, corr_thr, hit_thr,
+               int(buffer_forward), int(nondir), S, ctl.ctypes.data,
+               None if co is None else co.ctypes.data,
+               0 if co is None else co.size, contig, pos.size, pos.ctypes.data,
+               None if cf is None else cf.ctypes.data,
+               None if cr is None else cr.ctypes.data,
+               out.ctypes.data, sums.ctypes.data, cap, *extra)
         assert n <= cap
         return out[:n], sums[:n]
+
+    def run_unit(self, bw, background, pos, counts_fwd, counts_rev=None, *, region_thr=25.0,
+                 kurt_thr=50.0, corr_thr=-1.0, hit_thr=10.0, buffer_forward=True,
+                 nondir=False, control=None, coeffs=None, contig=0, cap=1 << 16):
+        """All candidate regions (accepted and rejected) of one unit."""
+        return self._run_unit(self.L.orc_run_unit, (), bw, background, pos, counts_fwd, counts_rev,
+                              region_thr, kurt_thr, corr_thr, hit_thr, buffer_forward, nondir, control,
+                              coeffs, contig, cap)
+
+    def run_unit_shifts(self, bw, background, pos, counts_fwd, counts_rev=None, *, max_shift,
+                        region_thr=25.0, kurt_thr=50.0, corr_thr=-1.0, hit_thr=10.0,
+                        buffer_forward=True, nondir=False, control=None, coeffs=None, contig=0,
+                        cap=1 << 12):
+        """run_unit plus Region::strandCorr(0 .. max_shift) of every candidate
+        -> (regions, sums, table [n][max_shift + 1]) (orc_run_unit_shifts)"""
+        c = ctypes
+        # (bound here, not in __init__: a library built before the symbol
+        # existed still serves every other caller)
+        try:
+            fn = self.L.orc_run_unit_shifts
+        except AttributeError:
+            raise RuntimeError("liboracle.so has no orc_run_unit_shifts: it was built from an older "
+                               "oracle/; rebuild it with `make -C oracle`") from None
+        fn.restype = c.c_int64
+        fn.argtypes = self.L.orc_run_unit.argtypes + [c.c_uint16, c.c_void_p]
+        tab = np.full((cap, max_shift + 1), np.nan, np.float64)
+        regs, sums = self._run_unit(fn, (max_shift, tab.ctypes.data), bw, background, pos, counts_fwd,
+                                    counts_rev, region_thr, kurt_thr, corr_thr, hit_thr, buffer_forward,
+                                    nondir, control, coeffs, contig, cap)
+        return regs, sums, tab[:len(regs)].copy()
 
     def profile(self, bw, background, length, pos, counts_fwd, counts_rev=None, *,
                 buffer_forward=True, nondir=False, control=None, coeffs=None):

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 from tests import wide_nd_inputs as W
+from tests.shift_ref import host_shift_table
 from tests.test_cli import compare_tool, make_inputs, run
 from tests.test_gpu_replay import close, compare
 from tests.wig import write_contigs, write_wig
@@ -283,34 +284,6 @@ def test_index_states(gpu_lib, parity_ref, policy, passes):
 
 
 # ---- 8. K4 -------------------------------------------------------------------------
-
-def strand_corr(f, r, shift):
-    """Region::strandCorr(shift) (src/strand_shift.cpp:205-217, misc/data.cpp:
-    22-58, 184-193): sequential sums (np.cumsum adds in index order)"""
-    n = f.size
-    if not n > 2 * shift + 3:
-        return np.nan
-    m = n - 2 * shift
-    a, b = f[:m], r[2 * shift:2 * shift + m]
-    seq = lambda v: np.cumsum(v)[-1]
-    m1, m2 = seq(a) / m, seq(b) / m
-    with np.errstate(invalid="ignore", divide="ignore"):
-        sd1 = np.sqrt(seq((a - m1) * (a - m1)) / (m - 1.0))
-        sd2 = np.sqrt(seq((b - m2) * (b - m2)) / (m - 1.0))
-        return seq((a - m1) * (b - m2)) / ((m - 1.0) * sd1 * sd2)
-
-
-def host_shift_table(oracle, bw, bg, pos, cf, cr, regs, max_shift):
-    """strandCorr(0 .. max_shift) of the given regions of one unit over f =
-    the oracle's dense profile of the forward counts alone and r = that of the
-    reverse counts alone (regions the K0 head chain did not emit)"""
-    span = int(regs["right"].max())
-    mf, mr = cf[:, 0] != 0, cr[:, 0] != 0
-    f = oracle.profile(bw, bg, span, pos[mf], cf[mf])
-    r = oracle.profile(bw, bg, span, pos[mr], cr[mr])
-    return np.array([[strand_corr(f[q["left"] - 1:q["right"]], r[q["left"] - 1:q["right"]], s)
-                      for s in range(max_shift + 1)] for q in regs]).reshape(len(regs), max_shift + 1)
-
 
 def shift_tables(g, oracle, bw, length, pos, cf, cr, max_shift):
     """(up_shift_scan's table, the host recomputation) of every region of one

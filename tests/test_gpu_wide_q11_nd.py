@@ -22,9 +22,9 @@ import numpy as np
 import pytest
 
 from tests import wide_q11_nd_inputs as N
+from tests.shift_ref import host_shift_table
 from tests.test_cli import BIN, compare_tool, make_inputs
 from tests.test_gpu_replay import close, compare
-from tests.test_gpu_wide_nondir import host_shift_table
 from tests.wig import write_contigs, write_wig
 
 pytestmark = pytest.mark.gpu

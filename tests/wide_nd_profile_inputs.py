@@ -18,7 +18,7 @@ POOL_COEFFS = [None, [0.6, 1.7]]
 def strand_refs(oracle, bw, bg, length, pos, cf, cr, **kw):
     """(f, r, f + r as the oracle's nondirectional profile): f the oracle's
     profile of the forward counts alone, r that of the reverse counts alone
-    (host_shift_table's idiom in tests/test_gpu_wide_nondir.py); read-only"""
+    (host_shift_table's idiom in tests/shift_ref.py); read-only"""
     mf, mr = cf.any(axis=1), cr.any(axis=1)
     f = oracle.profile(bw, bg, length, pos[mf], cf[mf], **kw)
     r = oracle.profile(bw, bg, length, pos[mr], cr[mr], **kw)
