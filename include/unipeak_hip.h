@@ -29,6 +29,8 @@
  *   up_get_regions      <- regionsOut vector + Region statistics
  *                          misc/peakcall.cpp:45, misc/data.cpp:104-193
  *   up_shift_scan       <- Region::strandCorr(shift) loop src/strand_shift.cpp:205-228
+ *   up_unit_profile_text <- FormatOutStream::write(PosScore), the -w lines
+ *                          misc/format.cpp:1091-1132
  *
  * Conventions: plain C types only; the caller owns host buffers, the library
  * owns device memory; one context per GPU, driven by one host thread (not
@@ -114,6 +116,15 @@ int up_device_count(int *n);
 
 /* Kernel::Kernel(bw, sum) -- 2*bw+1 weights into w (host computation). */
 int up_kernel_weights(uint16_t bw, double sum, double *w);
+
+#define UP_G6_MAX 16
+/* printf("%g", v) into out (no terminator, at most UP_G6_MAX bytes), host
+ * computation, the routine the device formatter runs (csrc/fmt_g6.h: six
+ * digits correctly rounded from the exact binary value in integer arithmetic);
+ * *n = bytes written, 0 when v is outside the range that routine formats
+ * itself: it formats every finite v with 2^-67 <= |v| < 2^60 (which contains
+ * 1e-20 <= |v| < 1e18) and nothing else -- not 0, subnormals, NaN, infinities */
+int up_format_g6(double v, char *out, int *n);
 
 int up_open(int hip_device, up_ctx **out);
 void up_close(up_ctx *ctx);
@@ -334,7 +345,9 @@ int up_scan_density(up_ctx *ctx, uint32_t *bytes_per_1024);
  * also [5]=the dense-profile kernel of the last up_unit_profile* call (HIP
  * events around it); with n > 6 also [6]=K0 and [7]=the placement kernels of
  * the last pass that placed its head units itself (up_set_head_place) at
- * timing level 2, else 0 */
+ * timing level 2, else 0; with n > 8 also [8]=the text kernels of the last
+ * up_unit_profile_text call (HIP events around them; [5] is then that call's
+ * dense-profile kernel) */
 /* achievable HBM rate: a float4 streaming copy kernel of `bytes` (a multiple
  * of 16; best of reps),
  * GB/s counting read + write (the bench's copy-rate reference) */
@@ -380,6 +393,27 @@ int up_unit_replay_profile(up_ctx *ctx, uint32_t unit, uint32_t *resync, uint64_
  * NULL for directional units */
 int up_unit_profile_range(up_ctx *ctx, uint32_t unit, uint64_t first, uint32_t count,
                           double *out_f, double *out_r);
+/* -w as text: the lines FormatOutStream::write(PosScore) writes for positions
+ * [first, first + count) of one unit -- "<pos> <score>\n" for every position
+ * whose f + r is not 0, ascending, score as printf("%g") (negate != 0: "-"
+ * before the score, the reverse buffer of a directional run) -- formatted on
+ * the device (csrc/proftext.hip) from the same dense scores
+ * up_unit_profile_range returns; f + r is one IEEE add.
+ * cut_pos[n_cuts] (non-decreasing, each in [first, first + count]) asks for
+ * cut_off[i] = the bytes of the lines at positions < cut_pos[i].
+ * *text: host memory owned by the context (pinned), valid until the next
+ * call that runs a pass, formats text, resets the units or closes it; NULL
+ * when the range has no line (*n_bytes = 0, *exact = 1).
+ * *exact = 0: the range holds a score outside up_format_g6's range (or NaN /
+ * infinity; or |score| >= UNIPEAK_PROFILE_TEXT_LIMIT, a test-only variable
+ * read at up_open); *text is NULL, *n_bytes and *n_lines 0, cut_off untouched,
+ * and the caller formats this range from up_unit_profile_range.
+ * Arguments, states and refusals as up_unit_profile_range's (both strands are
+ * always summed, so there is no out_r rule). */
+int up_unit_profile_text(up_ctx *ctx, uint32_t unit, uint64_t first, uint32_t count,
+                         int32_t negate, uint32_t n_cuts, const uint64_t *cut_pos,
+                         uint64_t *cut_off, const char **text, uint64_t *n_bytes,
+                         uint64_t *n_lines, int32_t *exact);
 /* nondirectional units above UP_MAX_PARALLEL_BW (bw 512..32767, threshold > 0):
  * 0 (default): K1w only inside the blocking up_run with the -w capture off;
  *    up_run_async and up_unit_profile* refused, the capture keeps the replay.

@@ -71,14 +71,14 @@ EXPORTS = [
     "up_unit_scatter", "up_unit_synth", "up_unit_synth_offset", "up_unit_synth_ex", "up_unit_tag_total", "up_unit_set_last_add", "up_unit_last_add",
     "up_reset_units", "up_run", "up_get_regions", "up_regions_view", "up_shift_scan", "up_shift_best",
     "up_timings", "up_scan_density", "up_unit_profile", "up_hbm_copy_gbps", "up_set_record_target",
-    "up_host_register", "up_unit_profile_range", "up_run_async", "up_run_wait", "up_set_timing",
+    "up_host_register", "up_unit_profile_range", "up_unit_profile_text", "up_run_async", "up_run_wait", "up_set_timing",
     "up_set_profile_capture", "up_unit_replay_profile", "up_set_wide_nd_full",
     "up_set_index_policy", "up_invalidate_index", "up_index_state", "up_last_stats_kind", "up_last_exact_kind",
     "up_last_scan_kind", "up_set_head_place", "up_last_head_kind",
     "up_tir_open", "up_tir_close", "up_tir_set_stream", "up_tir_query", "up_tir_timings",
     "up_cm_open", "up_cm_close", "up_cm_add", "up_cm_collect", "up_cm_timings",
 ]
-# (up_set_wide_q11_nd is bound in load_library like the rest; it is not listed here because
+# (up_set_wide_q11_nd and up_format_g6 are bound in load_library like the rest; they are not listed here because
 # tests/test_capi.py compares this list with the header's names as its pattern reads them,
 # letters and underscores only)
 TIR_HOST = 0xFFFFFFFF  # UP_TIR_HOST
@@ -101,6 +101,7 @@ def load_library(path=LIB_PATH):
         "up_strerror": (c.c_char_p, [c.c_int]),
         "up_device_count": (c.c_int, [c.POINTER(c.c_int)]),
         "up_kernel_weights": (c.c_int, [c.c_uint16, c.c_double, vp]),
+        "up_format_g6": (c.c_int, [c.c_double, vp, c.POINTER(c.c_int)]),
         "up_open": (c.c_int, [c.c_int, c.POINTER(vp)]),
         "up_close": (None, [vp]),
         "up_set_params": (c.c_int, [vp, c.POINTER(Params)]),
@@ -141,6 +142,9 @@ def load_library(path=LIB_PATH):
         "up_set_record_target": (c.c_int, [vp, vp, c.c_uint64]),
         "up_host_register": (c.c_int, [vp, vp, c.c_uint64]),
         "up_unit_profile_range": (c.c_int, [vp, c.c_uint32, c.c_uint64, c.c_uint32, vp, vp]),
+        "up_unit_profile_text": (c.c_int, [vp, c.c_uint32, c.c_uint64, c.c_uint32, c.c_int32, c.c_uint32, vp, vp,
+                                           c.POINTER(vp), c.POINTER(c.c_uint64), c.POINTER(c.c_uint64),
+                                           c.POINTER(c.c_int32)]),
         "up_set_profile_capture": (c.c_int, [vp, c.c_int]),
         "up_set_wide_nd_full": (c.c_int, [vp, c.c_int]),
         "up_set_wide_q11_nd": (c.c_int, [vp, c.c_int]),
@@ -179,6 +183,16 @@ def kernel_weights(bw, total=1.0):
     w = np.zeros(2 * bw + 1, np.float64)
     _ck(L.up_kernel_weights(bw, total, w.ctypes.data))
     return w
+
+
+def format_g6(v):
+    """printf("%g", v) as bytes by the routine the device formatter runs, or None when
+    v is outside the range it formats itself (up_format_g6)"""
+    L = load_library()
+    buf = ctypes.create_string_buffer(16)  # UP_G6_MAX
+    n = ctypes.c_int(0)
+    _ck(L.up_format_g6(float(v), buf, ctypes.byref(n)))
+    return buf.raw[:n.value] if n.value else None
 
 
 def track_bits():
@@ -413,6 +427,30 @@ class Lib:
         t = np.zeros(6, np.float64)
         _ck(self.L.up_timings(self.ctx, t.ctypes.data, 6))
         return float(t[5])
+
+    def profile_text(self, unit, first, count, negate=False, cuts=None):
+        """the -w lines of positions [first, first + count) formatted on the device:
+        (text bytes or None, cut_off uint64[], n_lines, exact); cuts: non-decreasing
+        positions in [first, first + count] whose byte offsets are wanted; exact False:
+        the range holds a score the device does not format, text None
+        (up_unit_profile_text)"""
+        cp = np.ascontiguousarray(cuts if cuts is not None else [], np.uint64)
+        co = np.zeros(len(cp), np.uint64)
+        text, nb, nl, ex = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int32()
+        _ck(self.L.up_unit_profile_text(self.ctx, unit, first, count, int(bool(negate)), len(cp),
+                                        cp.ctypes.data if len(cp) else None,
+                                        co.ctypes.data if len(cp) else None, ctypes.byref(text),
+                                        ctypes.byref(nb), ctypes.byref(nl), ctypes.byref(ex)))
+        if not ex.value:
+            return None, co, 0, False
+        data = ctypes.string_at(text.value, nb.value) if nb.value else b""
+        return data, co, nl.value, True
+
+    def profile_text_ms(self):
+        """device time of the text kernels of the last profile_text() (up_timings [8])"""
+        t = np.zeros(9, np.float64)
+        _ck(self.L.up_timings(self.ctx, t.ctypes.data, 9))
+        return float(t[8])
 
     def set_profile_capture(self, on):
         _ck(self.L.up_set_profile_capture(self.ctx, int(bool(on))))

@@ -29,6 +29,7 @@
 #include "q11place.hip"
 #include "headplace.hip"
 #include "wide.hip"
+#include "proftext.hip"
 
 namespace upk {
 // the templated K1 / K3 / K4 kernels live in eight translation units, one per
@@ -185,6 +186,19 @@ struct up_ctx {
     Event ev[8];
     double times[5] = {0, 0, 0, 0, 0};
     double prof_ms = 0;  // the dense-profile kernel of the last up_unit_profile* (HIP events)
+    // up_unit_profile_text (proftext.hip): code words, per-workgroup bytes and
+    // lines + the flag, workgroup prefix, the text on the device and in pinned
+    // host memory, cuts (positions, then offsets), pinned totals (bytes, lines,
+    // flag); its kernels' time (up_timings [8]); scores with |v| >= text_limit
+    // count as not formatted (test-only, read at up_open: UNIPEAK_PROFILE_TEXT_LIMIT)
+    DevBuf<uint32_t> d_pt_code, d_pt_blk;
+    DevBuf<uint64_t> d_pt_off, d_pt_cut;
+    DevBuf<uint8_t> d_pt_text;
+    HostBuf<uint8_t> h_pt_text;
+    HostBuf<uint64_t> h_pt_tot;
+    Event pt_ev[4];
+    double text_ms = 0;
+    double text_limit = HUGE_VAL;
     int timing = 2;                  // up_set_timing: 0 wall only, 1 + K1a, 2 every phase
     // passes in flight (up_run_async); slot = sequence % kSlots.  Each slot
     // owns its device buffers and its stream, so a pass's streaming K1a can
@@ -480,6 +494,15 @@ int up_kernel_weights(uint16_t bw, double sum, double *w) {
     return UP_OK;
 }
 
+// printf("%g", v) by the routine the device formatter runs (fmt_g6.h)
+int up_format_g6(double v, char *out, int *n) {
+    if (!out || !n) return UP_E_ARG;
+    uint64_t bits;
+    memcpy(&bits, &v, sizeof bits);
+    *n = g6_format(bits, out);
+    return UP_OK;
+}
+
 int up_open(int hip_device, up_ctx **out) {
     if (!out) return UP_E_ARG;
     int n = 0;
@@ -501,6 +524,7 @@ int up_open(int hip_device, up_ctx **out) {
     if (const char *e = getenv("UNIPEAK_WIDE_Q11_ND")) c->wide_q11_nd_env = atoi(e) != 0;
     if (const char *e = getenv("UNIPEAK_WIDE_CORR_LONG")) c->corr_long = std::max<uint64_t>(4, strtoull(e, nullptr, 10));
     if (const char *e = getenv("UNIPEAK_WIDE_CORR_TILE")) c->corr_tile = std::max<uint64_t>(64, strtoull(e, nullptr, 10));
+    if (const char *e = getenv("UNIPEAK_PROFILE_TEXT_LIMIT")) c->text_limit = strtod(e, nullptr);
     if (const char *e = getenv("UNIPEAK_K1B_BLOCKS")) c->k1b_blocks = std::max(0, atoi(e));
     if (const char *e = getenv("UNIPEAK_CHAINS")) c->n_chain = std::min(4, std::max(1, atoi(e)));
     if (const char *e = getenv("UNIPEAK_LAUNCHER")) c->use_launcher = e[0] != '0';
@@ -523,6 +547,7 @@ int up_open(int hip_device, up_ctx **out) {
         for (int i = 0; i < c->n_chain; ++i) HIPCHK(hipStreamCreateWithFlags(&c->chain[i], hipStreamNonBlocking));
     }
     for (auto &e : c->ev) HIPCHK(hipEventCreate(&e));
+    for (auto &e : c->pt_ev) HIPCHK(hipEventCreate(&e));
     for (auto &ps : c->pass) {
         for (auto &e : ps.ev) HIPCHK(hipEventCreate(&e));
         for (auto &e : ps.hev) HIPCHK(hipEventCreate(&e));
@@ -3600,29 +3625,34 @@ int up_timings(up_ctx *c, double *ms, int n) {
     for (int i = 0; i < n && i < 5; ++i) ms[i] = c->times[i];
     if (n > 5) ms[5] = c->prof_ms;
     for (int i = 6; i < n && i < 8; ++i) ms[i] = c->head_ms[i - 6];
+    if (n > 8) ms[8] = c->text_ms;
     return UP_OK;
 }
 
-int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t count, double *out_f,
-                          double *out_r) {
+// The dense f and r of positions [first, first + count) of a unit into scratch
+// of the call, on the context's stream (not waited for): *d_f, and *d_r four-
+// position aligned behind it, both zero-filled up to a multiple of four
+// positions.  The checks of up_unit_profile_range that do not concern its
+// output arrays; up_timings [5] once the caller has drained the stream
+// (profile_dense_time).
+static int profile_dense(up_ctx *c, uint32_t unit, uint64_t first, uint32_t count, StreamScratch &scratch,
+                         double **d_f, double **d_r) {
     int r = check_runnable(c, true);
     if (r) return r;
     if (busy(c)) return UP_E_STATE;  // a pass in flight reads this state
-    if (unit >= c->units.size() || !out_f || first < 1 || count == 0) return UP_E_ARG;
-    // both strands' scores are the answer (K1w, or wide K1q behind up_set_wide_q11_nd)
-    if (!out_r && c->p.nondir && c->p.bw > kMaxBw) return UP_E_ARG;
+    if (unit >= c->units.size() || first < 1 || count == 0) return UP_E_ARG;
     HIPCHK(hipSetDevice(c->dev));
     if ((r = sync_units(c))) return r;
     const Unit &u = c->units[unit];
     const uint64_t dom = (uint64_t)u.nstrips * kStrip;  // scan domain incl. Q16 tail
     if (first + count - 1 > dom) return UP_E_ARG;
-    StreamScratch scratch(c->stream);
+    const size_t pad = ((size_t)count + 3) & ~(size_t)3;
     double *d = nullptr;
-    HIPCHK(scratch.alloc(&d, 2 * (size_t)count * sizeof(double) + 16));
-    HIPCHK(hipMemsetAsync(d, 0, 2 * (size_t)count * sizeof(double), c->stream));
+    HIPCHK(scratch.alloc(&d, 2 * pad * sizeof(double) + 16));
+    HIPCHK(hipMemsetAsync(d, 0, 2 * pad * sizeof(double), c->stream));
     ScanParams P = scan_params(c, c->pass[0], c->ovf_cap);  // no pass in flight; records unused
     P.prof_f = d;
-    P.prof_r = d + count;
+    P.prof_r = d + pad;
     P.prof_first = (int64_t)first;
     P.prof_len = count;
     P.prof_unit = unit;
@@ -3647,14 +3677,102 @@ int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t cou
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev[6], c->stream));
+    *d_f = d;
+    *d_r = d + pad;
+    return UP_OK;
+}
+
+static void profile_dense_time(up_ctx *c) {
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[6]);
+    c->prof_ms = ms;
+}
+
+int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t count, double *out_f,
+                          double *out_r) {
+    int r = check_runnable(c, true);
+    if (r) return r;
+    if (busy(c)) return UP_E_STATE;
+    if (!out_f) return UP_E_ARG;
+    // both strands' scores are the answer (K1w, or wide K1q behind up_set_wide_q11_nd)
+    if (!out_r && c->p.nondir && c->p.bw > kMaxBw) return UP_E_ARG;
+    StreamScratch scratch(c->stream);
+    double *d_f = nullptr, *d_r = nullptr;
+    if ((r = profile_dense(c, unit, first, count, scratch, &d_f, &d_r))) return r;
     HIPCHK(hipStreamSynchronize(c->stream));
-    {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, c->ev[5], c->ev[6]);
-        c->prof_ms = ms;
+    profile_dense_time(c);
+    HIPCHK(hipMemcpy(out_f, d_f, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_r) HIPCHK(hipMemcpy(out_r, d_r, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    return UP_OK;
+}
+
+int up_unit_profile_text(up_ctx *c, uint32_t unit, uint64_t first, uint32_t count, int32_t negate,
+                         uint32_t n_cuts, const uint64_t *cut_pos, uint64_t *cut_off, const char **text,
+                         uint64_t *n_bytes, uint64_t *n_lines, int32_t *exact) {
+    int r = check_runnable(c, true);
+    if (r) return r;
+    if (busy(c)) return UP_E_STATE;
+    if (!text || !n_bytes || !n_lines || !exact || (n_cuts && (!cut_pos || !cut_off))) return UP_E_ARG;
+    for (uint32_t i = 0; i < n_cuts; ++i)
+        if (cut_pos[i] < first || cut_pos[i] > first + count || (i && cut_pos[i] < cut_pos[i - 1])) return UP_E_ARG;
+    if (first + count > 9999999999ull) return UP_E_ARG;  // (kPtPosMax digits; no scan domain is that long)
+    *text = nullptr;
+    *n_bytes = *n_lines = 0;
+    *exact = 0;
+    StreamScratch scratch(c->stream);
+    double *d_f = nullptr, *d_r = nullptr;
+    if ((r = profile_dense(c, unit, first, count, scratch, &d_f, &d_r))) return r;
+    const uint32_t nblk = (uint32_t)(((uint64_t)count + kPtBlock - 1) / kPtBlock);
+    HIPCHK(c->d_pt_code.ensure((size_t)nblk * kPtBlock));
+    HIPCHK(c->d_pt_blk.ensure(2 * (size_t)nblk + 1));
+    HIPCHK(c->d_pt_off.ensure((size_t)nblk + 1 + 3));
+    HIPCHK(c->h_pt_tot.ensure(3));
+    uint32_t *blk_bytes = c->d_pt_blk.p, *blk_lines = blk_bytes + nblk, *flag = blk_lines + nblk;
+    uint64_t *blk_off = c->d_pt_off.p, *totals = blk_off + nblk + 1;
+    const int neg = negate != 0;
+    HIPCHK(hipMemsetAsync(flag, 0, sizeof(uint32_t), c->stream));
+    HIPCHK(hipEventRecord(c->pt_ev[0], c->stream));
+    hipLaunchKernelGGL(proftext_len_kernel, dim3(nblk), dim3(kPtThreads), 0, c->stream, d_f, d_r, first, count, neg,
+                       c->text_limit, c->d_pt_code.p, blk_bytes, blk_lines, flag);
+    hipLaunchKernelGGL(proftext_scan_kernel, dim3(1), dim3(kPtThreads), 0, c->stream, blk_bytes, blk_lines, nblk,
+                       flag, blk_off, totals);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->pt_ev[1], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_pt_tot.p, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    profile_dense_time(c);
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, c->pt_ev[0], c->pt_ev[1]);
+    c->text_ms = ms;
+    const uint64_t bytes = c->h_pt_tot.p[0], lines = c->h_pt_tot.p[1];
+    if (c->h_pt_tot.p[2]) return UP_OK;  // a score the digit routine does not format: *exact = 0
+    *exact = 1;
+    if (bytes) {
+        HIPCHK(c->d_pt_text.ensure(bytes + 4));
+        HIPCHK(c->h_pt_text.ensure(bytes));
     }
-    HIPCHK(hipMemcpy(out_f, d, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_r) HIPCHK(hipMemcpy(out_r, d + count, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    if (n_cuts) HIPCHK(c->d_pt_cut.ensure(2 * (size_t)n_cuts));
+    HIPCHK(hipEventRecord(c->pt_ev[2], c->stream));
+    if (bytes)
+        hipLaunchKernelGGL(proftext_write_kernel, dim3(nblk), dim3(kPtThreads), 0, c->stream, c->d_pt_code.p, blk_off,
+                           first, neg, c->d_pt_text.p);
+    if (n_cuts) {
+        uint64_t *d_cp = c->d_pt_cut.p, *d_co = d_cp + n_cuts;
+        HIPCHK(hipMemcpyAsync(d_cp, cut_pos, n_cuts * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(proftext_cut_kernel, dim3(n_cuts), dim3(64), 0, c->stream, c->d_pt_code.p, blk_off, nblk,
+                           first, count, neg, d_cp, n_cuts, d_co);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->pt_ev[3], c->stream));
+    if (bytes) HIPCHK(hipMemcpyAsync(c->h_pt_text.p, c->d_pt_text.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (n_cuts)
+        HIPCHK(hipMemcpy(cut_off, c->d_pt_cut.p + n_cuts, n_cuts * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    (void)hipEventElapsedTime(&ms, c->pt_ev[2], c->pt_ev[3]);
+    c->text_ms += ms;
+    if (bytes) *text = (const char *)c->h_pt_text.p;
+    *n_bytes = bytes;
+    *n_lines = lines;
     return UP_OK;
 }
 

@@ -598,8 +598,7 @@ void ProfileSink::header() {  // FormatOutStream::trackHeader, format.cpp:1164-1
     std::fputc('\n', fp);
 }
 
-void ProfileSink::write(bool fwd, uint32_t c, uint64_t pos, double score) {
-    if (score == 0) return;  // format.cpp:1092
+void ProfileSink::start_line(bool fwd, uint32_t c) {
     if (directional) {
         if (!have_contig || forward != fwd) {
             forward = fwd;
@@ -614,8 +613,20 @@ void ProfileSink::write(bool fwd, uint32_t c, uint64_t pos, double score) {
         have_contig = true;
         std::fprintf(fp, "variableStep chrom=%s\n", ct->name(c).c_str());
     }
+}
+
+void ProfileSink::write(bool fwd, uint32_t c, uint64_t pos, double score) {
+    if (score == 0) return;  // format.cpp:1092
+    start_line(fwd, c);
+    ++stats.host_lines;
     // ostream << double: 6 significant digits (%g); reverse strand negated
     std::fprintf(fp, (directional && !fwd) ? "%llu -%g\n" : "%llu %g\n", (unsigned long long)pos, score);
+}
+
+void ProfileSink::write_block(bool fwd, uint32_t c, const char *text, size_t n) {
+    if (!n) return;  // the reference switches headers only when it writes a line
+    start_line(fwd, c);
+    if (std::fwrite(text, 1, n, fp) != n) fatal("-w: short write of the profile");
 }
 
 void write_profile(const PassResult &pr, uint16_t bw, ProfileSink &sink) {
@@ -683,32 +694,127 @@ void write_profile(const PassResult &pr, uint16_t bw, ProfileSink &sink) {
     std::stable_sort(ev.begin(), ev.end(), [](const Ev &a, const Ev &b) {
         return a.t != b.t ? a.t < b.t : a.kind < b.kind;
     });
-    // per-unit cache of one chunk of the device profile
-    constexpr uint32_t kChunkPos = 1u << 22;
-    struct Cache { int64_t first = -1; std::vector<double> f, r; };
+    // One chunk of a unit's dense profile at a time, chunk-aligned.  By default
+    // the device formats the chunk's lines itself (up_unit_profile_text) and
+    // the host only slices that text; a chunk the device does not format
+    // exactly (exact = 0), a refused call and UNIPEAK_PROFILE_TEXT=0 keep the
+    // scores and sink.write().
+    uint32_t chunk_pos = 1u << 22;
+    if (const char *e = std::getenv("UNIPEAK_PROFILE_TEXT_CHUNK")) {  // tests: slices across chunk edges
+        const unsigned long long v = std::strtoull(e, nullptr, 10);
+        if (v >= 64 && v <= (1ull << 30)) chunk_pos = (uint32_t)v;
+    }
+    const char *et = std::getenv("UNIPEAK_PROFILE_TEXT");
+    const bool use_text = !(et && et[0] == '0');
+    // A maximal run of time-consecutive dense events of one unit is one slice
+    // [lo, hi): a unit's events are ascending and disjoint and the positions
+    // between them have no tag within bw, so no line; the concatenation of a
+    // unit's slices is its text.  The slice ends are the cuts of their chunks.
+    struct Slice { uint32_t unit; int64_t lo, hi; };
+    std::vector<Slice> slices;  // in emission order; kind-0 events keep their place through `at`
+    std::vector<size_t> at(ev.size(), ~(size_t)0);  // event -> the slice it starts (kind 1), else none
+    std::vector<std::vector<uint64_t>> cuts(pr.units.size());
+    for (size_t i = 0; i < ev.size();) {
+        if (ev[i].kind == 0) {
+            ++i;
+            continue;
+        }
+        size_t j = i;
+        while (j + 1 < ev.size() && ev[j + 1].kind == 1 && ev[j + 1].unit == ev[i].unit) ++j;
+        at[i] = slices.size();
+        slices.push_back({ev[i].unit, ev[i].lo, ev[j].hi + 1});
+        cuts[ev[i].unit].push_back((uint64_t)ev[i].lo);
+        cuts[ev[i].unit].push_back((uint64_t)ev[j].hi + 1);
+        i = j + 1;
+    }
+    struct Cache {
+        int64_t first = -1;
+        uint32_t n = 0;
+        bool text = false;
+        std::string bytes;                  // text: the chunk's lines
+        std::vector<uint64_t> cpos, coff;   // text: its cuts and their byte offsets
+        std::vector<double> f, r;           // else: its scores
+    };
     std::vector<Cache> cache(pr.units.size());
-    for (const Ev &e : ev) {
+    ProfileStats &st = sink.stats;
+    auto load = [&](uint32_t unit, int64_t x) {  // the chunk that holds position x
+        Cache &c = cache[unit];
+        const UnitBuild &u = pr.units[unit];
+        c.first = ((x - 1) / chunk_pos) * (int64_t)chunk_pos + 1;
+        const uint64_t dom_end = (uint64_t)u.len + bw;  // highest position a flush retires
+        c.n = (uint64_t)c.first > dom_end
+                  ? 0 : (uint32_t)std::min<uint64_t>(chunk_pos, dom_end - (uint64_t)c.first + 1);
+        c.text = false;
+        if (!c.n) return;  // beyond the scan domain: never scored
+        ++st.chunks;
+        if (use_text) {
+            const std::vector<uint64_t> &all = cuts[unit];
+            const auto a = std::lower_bound(all.begin(), all.end(), (uint64_t)c.first);
+            const auto b = std::upper_bound(all.begin(), all.end(), (uint64_t)c.first + c.n);
+            c.cpos.assign(a, b);
+            c.coff.assign(c.cpos.size(), 0);
+            const char *text = nullptr;
+            uint64_t nb = 0, nl = 0;
+            int32_t exact = 0;
+            const int rc = up_unit_profile_text(where[unit].first, where[unit].second, (uint64_t)c.first, c.n,
+                                                sink.directional && u.buffer != 0, (uint32_t)c.cpos.size(),
+                                                c.cpos.data(), c.coff.data(), &text, &nb, &nl, &exact);
+            if (rc == UP_OK) {
+                double ms[9] = {0};
+                if (up_timings(where[unit].first, ms, 9) == UP_OK) {
+                    st.dense_ms += ms[5];
+                    st.text_ms += ms[8];
+                }
+            }
+            if (rc == UP_OK && exact) {
+                c.text = true;
+                c.bytes.assign(text ? text : "", nb);
+                st.device_bytes += nb;
+                st.device_lines += nl;
+                return;
+            }
+            ++st.fallback_chunks;
+        }
+        c.f.assign(c.n, 0.0);
+        c.r.assign(c.n, 0.0);
+        const int rc = up_unit_profile_range(where[unit].first, where[unit].second, (uint64_t)c.first, c.n,
+                                             c.f.data(), c.r.data());
+        if (rc != UP_OK) fatal(std::string("up_unit_profile_range: ") + up_strerror(rc));
+        double ms[6] = {0};
+        if (up_timings(where[unit].first, ms, 6) == UP_OK) st.dense_ms += ms[5];
+    };
+    auto offset_of = [](const Cache &c, uint64_t x) -> uint64_t {  // bytes of the chunk's lines below x
+        if (x == (uint64_t)c.first) return 0;
+        if (x == (uint64_t)c.first + c.n) return c.bytes.size();
+        const auto it = std::lower_bound(c.cpos.begin(), c.cpos.end(), x);
+        if (it == c.cpos.end() || *it != x) fatal("-w: a slice end is not among its chunk's cuts");
+        return c.coff[it - c.cpos.begin()];
+    };
+    for (size_t i = 0; i < ev.size(); ++i) {
+        const Ev &e = ev[i];
         const UnitBuild &u = pr.units[e.unit];
         if (e.kind == 0) {
             const Replayed &r = rep[e.unit];
-            for (int64_t i = e.lo; i < e.hi; ++i) sink.write(u.buffer == 0, u.contig, r.pos[i], r.score[i]);
+            for (int64_t k = e.lo; k < e.hi; ++k) sink.write(u.buffer == 0, u.contig, r.pos[k], r.score[k]);
             continue;
         }
+        if (at[i] == ~(size_t)0) continue;  // inside a slice already written
+        const Slice &sl = slices[at[i]];
         Cache &c = cache[e.unit];
-        for (int64_t x = e.lo; x <= e.hi; ++x) {
-            if (c.first < 0 || x < c.first || x >= c.first + (int64_t)kChunkPos) {
-                c.first = ((x - 1) / kChunkPos) * kChunkPos + 1;
-                const uint64_t dom_end = (uint64_t)u.len + bw;  // highest position a flush retires
-                const uint32_t n = (uint32_t)std::min<uint64_t>(kChunkPos, dom_end - (uint64_t)c.first + 1);
-                c.f.assign(n, 0.0);
-                c.r.assign(n, 0.0);
-                const int rc = up_unit_profile_range(where[e.unit].first, where[e.unit].second,
-                                                     (uint64_t)c.first, n, c.f.data(), c.r.data());
-                if (rc != UP_OK) fatal(std::string("up_unit_profile_range: ") + up_strerror(rc));
+        for (int64_t x = sl.lo; x < sl.hi;) {
+            if (c.first < 0 || x < c.first || x >= c.first + (int64_t)chunk_pos) load(e.unit, x);
+            const int64_t end = std::min<int64_t>(sl.hi, c.first + (int64_t)c.n);
+            if (end <= x) break;  // beyond the scan domain: never scored
+            if (c.text) {
+                const uint64_t o0 = offset_of(c, (uint64_t)x), o1 = offset_of(c, (uint64_t)end);
+                sink.write_block(u.buffer == 0, u.contig, c.bytes.data() + o0, o1 - o0);
+            } else {
+                for (int64_t y = x; y < end; ++y) {
+                    const size_t k = (size_t)(y - c.first);
+                    sink.write(u.buffer == 0, u.contig, (uint64_t)y, c.f[k] + c.r[k]);
+                }
             }
-            const size_t i = (size_t)(x - c.first);
-            if (i >= c.f.size()) continue;  // beyond the scan domain: never scored
-            sink.write(u.buffer == 0, u.contig, (uint64_t)x, c.f[i] + c.r[i]);
+            x = end;
         }
     }
 }

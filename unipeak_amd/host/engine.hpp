@@ -96,6 +96,14 @@ void shift_best(const EngineParams &ep, PassResult &out, const std::vector<const
 // nonzero score, written when the reference's processPosition writes it --
 // at the add() (or flush) that retires it, interleaved across the two
 // buffers by the replayed event clock (misc/format.cpp:1091-1132)
+// what write_profile did: lines and bytes the device formatted
+// (up_unit_profile_text), lines the host formatted, chunks fetched and how many
+// of them came back to the host path, device time of the kernels (ms)
+struct ProfileStats {
+    uint64_t device_bytes = 0, device_lines = 0, host_lines = 0, chunks = 0, fallback_chunks = 0;
+    double text_ms = 0, dense_ms = 0;
+};
+
 struct ProfileSink {
     std::FILE *fp = nullptr;
     const ContigTable *ct = nullptr;
@@ -103,8 +111,13 @@ struct ProfileSink {
     std::string name, assembly;
     bool have_contig = false, forward = true;
     uint32_t contig = 0;
+    ProfileStats stats;
     void header();
+    // the header / variableStep switches in front of a line of (fwd, contig)
+    void start_line(bool fwd, uint32_t contig);
     void write(bool fwd, uint32_t contig, uint64_t pos, double score);
+    // finished lines of (fwd, contig) in one piece; nothing for n = 0
+    void write_block(bool fwd, uint32_t contig, const char *text, size_t n);
 };
 void write_profile(const PassResult &pr, uint16_t bw, ProfileSink &sink);
 

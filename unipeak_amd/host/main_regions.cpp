@@ -228,6 +228,13 @@ int main(int argc, char **argv) {
         write_profile(pr, bw, prof);
         if (prof.fp != stdout) std::fclose(prof.fp); else std::fflush(stdout);
         timer.mark("profile");
+        if (const char *e = std::getenv("UNIPEAK_TIMING"); e && *e && *e != '0')
+            std::fprintf(stderr,
+                         "[timing] profile text: device %llu bytes %llu lines, host %llu lines, fallback chunks "
+                         "%llu of %llu, kernels text %.3f ms dense %.3f ms\n",
+                         (unsigned long long)prof.stats.device_bytes, (unsigned long long)prof.stats.device_lines,
+                         (unsigned long long)prof.stats.host_lines, (unsigned long long)prof.stats.fallback_chunks,
+                         (unsigned long long)prof.stats.chunks, prof.stats.text_ms, prof.stats.dense_ms);
     }
 
     // emission in the reference's order (Q2-Q4); Q3 drops final-flush regions
