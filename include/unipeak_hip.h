@@ -31,6 +31,8 @@
  *   up_shift_scan       <- Region::strandCorr(shift) loop src/strand_shift.cpp:205-228
  *   up_unit_profile_text <- FormatOutStream::write(PosScore), the -w lines
  *                          misc/format.cpp:1091-1132
+ *   up_unit_profile_bigwig <- the same lines through extras/wigs2bigwigs.pl
+ *                          (wigToBigWig -clip): items, sections, zoom records
  *
  * Conventions: plain C types only; the caller owns host buffers, the library
  * owns device memory; one context per GPU, driven by one host thread (not
@@ -125,6 +127,13 @@ int up_kernel_weights(uint16_t bw, double sum, double *w);
  * itself: it formats every finite v with 2^-67 <= |v| < 2^60 (which contains
  * 1e-20 <= |v| < 1e18) and nothing else -- not 0, subnormals, NaN, infinities */
 int up_format_g6(double v, char *out, int *n);
+/* (float)strtod of that text without making it, host computation, the routine
+ * the device's bigWig kernels run (csrc/fmt_g6.h: the six digits D and their
+ * exponent give the text's value D * 10^k; for |k| <= 22 one IEEE multiply or
+ * divide of two exact doubles is strtod's double, and the cast rounds it to
+ * float).  *ok = 0 (and *out = 0): v is outside up_format_g6's range, or its
+ * text is below 1e-17 (k < -22). */
+int up_g6_to_float(double v, float *out, int *ok);
 
 int up_open(int hip_device, up_ctx **out);
 void up_close(up_ctx *ctx);
@@ -347,7 +356,8 @@ int up_scan_density(up_ctx *ctx, uint32_t *bytes_per_1024);
  * the last pass that placed its head units itself (up_set_head_place) at
  * timing level 2, else 0; with n > 8 also [8]=the text kernels of the last
  * up_unit_profile_text call (HIP events around them; [5] is then that call's
- * dense-profile kernel) */
+ * dense-profile kernel); with n > 9 also [9]=the bigWig kernels of the last
+ * up_unit_profile_bigwig call (likewise) */
 /* achievable HBM rate: a float4 streaming copy kernel of `bytes` (a multiple
  * of 16; best of reps),
  * GB/s counting read + write (the bench's copy-rate reference) */
@@ -414,6 +424,53 @@ int up_unit_profile_text(up_ctx *ctx, uint32_t unit, uint64_t first, uint32_t co
                          int32_t negate, uint32_t n_cuts, const uint64_t *cut_pos,
                          uint64_t *cut_off, const char **text, uint64_t *n_bytes,
                          uint64_t *n_lines, int32_t *exact);
+/* -w as bigWig: what wigs2bigwigs (wigToBigWig -clip) makes of those lines,
+ * without the text.  An item is (start = pos - 1, value) of every position in
+ * [first, first + count) and <= clip_end (the contig's size) whose f + r is
+ * not 0; value = (float)strtod("<%g of f + r>"), negated for negate != 0 --
+ * up_g6_to_float's rule, not (float)(f + r).  Made on the device
+ * (csrc/bigwig.hip) from the dense scores of up_unit_profile_range:
+ *  items      ascending, the body of varStep sections of span 1;
+ *  sections   one record per 1,024 consecutive items of the call (the last
+ *             one shorter): extent [start, end), item count, min, max, and the
+ *             sums of v and v * v in double (a fixed order);
+ *  zoom[z]    the on-disk summary records (bbiSummaryOnDisk, 32 bytes) of
+ *             level z = 0 .. n_levels - 1 for the bins [j * R, (j + 1) * R) of
+ *             0-based starts that hold an item, R = reduction0 * 4^z, end
+ *             clipped at clip_end, chromId = chrom_id; sums are added in double
+ *             (level z + 1 from level z) and rounded to float once.
+ * (first - 1) must be a multiple of reduction0 * 4^(n_levels - 1) -- every bin
+ * of every level then lies inside the call -- else UP_E_ARG; n_levels <=
+ * UP_BW_MAX_LEVELS (0: no zoom, zoom and n_zoom may be NULL).
+ * The pointers are host memory owned by the context (pinned), valid until the
+ * next call that runs a pass, formats a profile, resets the units or closes it;
+ * NULL where the count is 0.
+ * *exact = 0: the range holds a score up_g6_to_float refuses (or |score| >=
+ * UNIPEAK_PROFILE_TEXT_LIMIT, the test-only variable of up_unit_profile_text);
+ * no outputs, and the caller converts the range from up_unit_profile_range.
+ * Arguments, states and refusals otherwise as up_unit_profile_range's.
+ * up_timings [9] = these kernels ([5] the call's dense-profile kernel). */
+#define UP_BW_MAX_LEVELS 10
+typedef struct {
+    uint32_t start; /* 0-based */
+    float value;
+} up_bw_item;
+typedef struct {
+    uint32_t start, end; /* first item's start, last item's start + 1 */
+    uint32_t count, pad;
+    float vmin, vmax;
+    double sum, sumsq;
+} up_bw_section;
+typedef struct {
+    uint32_t chrom, start, end, valid;
+    float vmin, vmax, sum, sumsq;
+} up_bw_zoom;
+int up_unit_profile_bigwig(up_ctx *ctx, uint32_t unit, uint64_t first, uint32_t count,
+                           int32_t negate, uint64_t clip_end, uint32_t reduction0,
+                           uint32_t n_levels, uint32_t chrom_id, const up_bw_item **items,
+                           uint64_t *n_items, const up_bw_section **sections,
+                           uint64_t *n_sections, const up_bw_zoom **zoom, uint64_t *n_zoom,
+                           int32_t *exact);
 /* nondirectional units above UP_MAX_PARALLEL_BW (bw 512..32767, threshold > 0):
  * 0 (default): K1w only inside the blocking up_run with the -w capture off;
  *    up_run_async and up_unit_profile* refused, the capture keeps the replay.

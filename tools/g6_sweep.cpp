@@ -1,7 +1,9 @@
 // tools/g6_sweep.cpp -- stand-alone host sweep of csrc/fmt_g6.h against
 // snprintf("%g"): the carries and ties, powers of ten and two with their
 // neighbours, every tie (n + 0.5) * 10^j of six-digit n for j = -3 .. 6, and N
-// seeded log-uniform values over 1e-20 .. 1e18.  Exit status 1 on a difference.
+// seeded log-uniform values over 1e-20 .. 1e18; and of g6_to_float against
+// (float)strtod of that text on the same values (answered exactly for texts
+// D * 10^k with |k| <= 22).  Exit status 1 on a difference.
 //
 //   g++ -O2 -std=c++17 -fsanitize=address,undefined -I unipeak_amd/csrc \
 //       -o build/g6_sweep tools/g6_sweep.cpp && build/g6_sweep [N]
@@ -13,7 +15,7 @@
 #include <cstring>
 #include <random>
 
-static long bad = 0, refused = 0;
+static long bad = 0, refused = 0, unanswered = 0;
 
 static void chk(double v) {
     uint64_t b;
@@ -35,6 +37,15 @@ static void chk(double v) {
     upk::g6_digits(b, &D, &X, &neg);
     if ((strcmp(o, r) || upk::g6_len(D, X, neg) != n || n > upk::kG6Max) && bad++ < 20)
         printf("%.17g: %s, snprintf %s\n", v, o, r);
+    // the float a reader of the text gets
+    uint32_t fb = 0, want;
+    const bool ok = upk::g6_to_float(b, &fb);
+    const float f = (float)strtod(r, nullptr);
+    memcpy(&want, &f, 4);
+    const bool inside = X - 5 >= -upk::kG6FloatMaxK && X - 5 <= upk::kG6FloatMaxK;
+    if ((ok != inside || (ok && fb != want)) && bad++ < 20)
+        printf("%.17g: float bits %08x (ok %d), strtod %08x\n", v, fb, (int)ok, want);
+    if (!ok) ++unanswered;
 }
 
 int main(int argc, char **argv) {
@@ -62,6 +73,7 @@ int main(int argc, char **argv) {
     std::mt19937_64 g(1);
     std::uniform_real_distribution<double> u(std::log(1e-20), std::log(1e18));
     for (long i = 0; i < N; ++i) chk(std::exp(u(g)));
-    printf("differences %ld, refused %ld (outside the range)\n", bad, refused);
+    printf("differences %ld, refused %ld (outside the range), no float for %ld (text below 1e-17)\n", bad, refused,
+           unanswered);
     return bad != 0;
 }

@@ -71,14 +71,14 @@ EXPORTS = [
     "up_unit_scatter", "up_unit_synth", "up_unit_synth_offset", "up_unit_synth_ex", "up_unit_tag_total", "up_unit_set_last_add", "up_unit_last_add",
     "up_reset_units", "up_run", "up_get_regions", "up_regions_view", "up_shift_scan", "up_shift_best",
     "up_timings", "up_scan_density", "up_unit_profile", "up_hbm_copy_gbps", "up_set_record_target",
-    "up_host_register", "up_unit_profile_range", "up_unit_profile_text", "up_run_async", "up_run_wait", "up_set_timing",
+    "up_host_register", "up_unit_profile_range", "up_unit_profile_text", "up_unit_profile_bigwig", "up_run_async", "up_run_wait", "up_set_timing",
     "up_set_profile_capture", "up_unit_replay_profile", "up_set_wide_nd_full",
     "up_set_index_policy", "up_invalidate_index", "up_index_state", "up_last_stats_kind", "up_last_exact_kind",
     "up_last_scan_kind", "up_set_head_place", "up_last_head_kind",
     "up_tir_open", "up_tir_close", "up_tir_set_stream", "up_tir_query", "up_tir_timings",
     "up_cm_open", "up_cm_close", "up_cm_add", "up_cm_collect", "up_cm_timings",
 ]
-# (up_set_wide_q11_nd and up_format_g6 are bound in load_library like the rest; they are not listed here because
+# (up_set_wide_q11_nd, up_format_g6 and up_g6_to_float are bound in load_library like the rest; they are not listed here because
 # tests/test_capi.py compares this list with the header's names as its pattern reads them,
 # letters and underscores only)
 TIR_HOST = 0xFFFFFFFF  # UP_TIR_HOST
@@ -102,6 +102,7 @@ def load_library(path=LIB_PATH):
         "up_device_count": (c.c_int, [c.POINTER(c.c_int)]),
         "up_kernel_weights": (c.c_int, [c.c_uint16, c.c_double, vp]),
         "up_format_g6": (c.c_int, [c.c_double, vp, c.POINTER(c.c_int)]),
+        "up_g6_to_float": (c.c_int, [c.c_double, c.POINTER(c.c_float), c.POINTER(c.c_int)]),
         "up_open": (c.c_int, [c.c_int, c.POINTER(vp)]),
         "up_close": (None, [vp]),
         "up_set_params": (c.c_int, [vp, c.POINTER(Params)]),
@@ -145,6 +146,10 @@ def load_library(path=LIB_PATH):
         "up_unit_profile_text": (c.c_int, [vp, c.c_uint32, c.c_uint64, c.c_uint32, c.c_int32, c.c_uint32, vp, vp,
                                            c.POINTER(vp), c.POINTER(c.c_uint64), c.POINTER(c.c_uint64),
                                            c.POINTER(c.c_int32)]),
+        "up_unit_profile_bigwig": (c.c_int, [vp, c.c_uint32, c.c_uint64, c.c_uint32, c.c_int32, c.c_uint64,
+                                             c.c_uint32, c.c_uint32, c.c_uint32, c.POINTER(vp),
+                                             c.POINTER(c.c_uint64), c.POINTER(vp), c.POINTER(c.c_uint64), vp, vp,
+                                             c.POINTER(c.c_int32)]),
         "up_set_profile_capture": (c.c_int, [vp, c.c_int]),
         "up_set_wide_nd_full": (c.c_int, [vp, c.c_int]),
         "up_set_wide_q11_nd": (c.c_int, [vp, c.c_int]),
@@ -193,6 +198,39 @@ def format_g6(v):
     n = ctypes.c_int(0)
     _ck(L.up_format_g6(float(v), buf, ctypes.byref(n)))
     return buf.raw[:n.value] if n.value else None
+
+
+def g6_to_float(v):
+    """(float)strtod(printf("%g", v)) as a numpy.float32 by the routine the device's bigWig
+    kernels run, or None when it refuses v: outside format_g6's range, or a text below
+    1e-17 (up_g6_to_float)"""
+    L = load_library()
+    out, ok = ctypes.c_float(0), ctypes.c_int(0)
+    _ck(L.up_g6_to_float(float(v), ctypes.byref(out), ctypes.byref(ok)))
+    return np.float32(out.value) if ok.value else None
+
+
+def g6_to_float_bits(values):
+    """up_g6_to_float over an array of doubles: (float32 bits as uint32[], ok as bool[])"""
+    L = load_library()
+    v = np.ascontiguousarray(values, np.float64)
+    bits, oks = np.zeros(v.size, np.uint32), np.zeros(v.size, bool)
+    out, ok = ctypes.c_float(0), ctypes.c_int(0)
+    po, pk, fn = ctypes.byref(out), ctypes.byref(ok), L.up_g6_to_float
+    view = ctypes.cast(ctypes.pointer(out), ctypes.POINTER(ctypes.c_uint32))
+    for i, x in enumerate(v.tolist()):
+        fn(x, po, pk)
+        bits[i] = view[0]
+        oks[i] = ok.value != 0
+    return bits, oks
+
+
+BW_ITEM_DTYPE = np.dtype([("start", "<u4"), ("value", "<f4")])  # up_bw_item
+BW_SECTION_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("count", "<u4"), ("pad", "<u4"),
+                             ("vmin", "<f4"), ("vmax", "<f4"), ("sum", "<f8"), ("sumsq", "<f8")])  # up_bw_section
+BW_ZOOM_DTYPE = np.dtype([("chrom", "<u4"), ("start", "<u4"), ("end", "<u4"), ("valid", "<u4"),
+                          ("vmin", "<f4"), ("vmax", "<f4"), ("sum", "<f4"), ("sumsq", "<f4")])  # up_bw_zoom
+BW_MAX_LEVELS = 10  # UP_BW_MAX_LEVELS
 
 
 def track_bits():
@@ -451,6 +489,40 @@ class Lib:
         t = np.zeros(9, np.float64)
         _ck(self.L.up_timings(self.ctx, t.ctypes.data, 9))
         return float(t[8])
+
+    def profile_bigwig(self, unit, first, count, negate=False, clip_end=None, reduction0=10, n_levels=0,
+                       chrom_id=0):
+        """the -w profile of positions [first, first + count) as bigWig pieces made on the
+        device: (items BW_ITEM_DTYPE[], sections BW_SECTION_DTYPE[], [zoom records
+        BW_ZOOM_DTYPE[] per level], exact); copies.  clip_end: the contig's size (default:
+        no clipping inside the range); exact False: the range holds a score the device does
+        not convert, the arrays are None (up_unit_profile_bigwig)"""
+        if clip_end is None:
+            clip_end = first + count
+        it, sec = ctypes.c_void_p(), ctypes.c_void_p()
+        ni, ns, ex = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int32()
+        nl = max(int(n_levels), 0)
+        zp = (ctypes.c_void_p * max(nl, 1))()
+        zn = (ctypes.c_uint64 * max(nl, 1))()
+        _ck(self.L.up_unit_profile_bigwig(self.ctx, unit, first, count, int(bool(negate)), clip_end, reduction0,
+                                          n_levels, chrom_id, ctypes.byref(it), ctypes.byref(ni), ctypes.byref(sec),
+                                          ctypes.byref(ns), ctypes.cast(zp, ctypes.c_void_p),
+                                          ctypes.cast(zn, ctypes.c_void_p), ctypes.byref(ex)))
+        if not ex.value:
+            return None, None, None, False
+
+        def arr(ptr, n, dt):
+            if not n:
+                return np.zeros(0, dt)
+            return np.frombuffer(ctypes.string_at(ptr, n * dt.itemsize), dt).copy()
+        return (arr(it.value, ni.value, BW_ITEM_DTYPE), arr(sec.value, ns.value, BW_SECTION_DTYPE),
+                [arr(zp[z], zn[z], BW_ZOOM_DTYPE) for z in range(nl)], True)
+
+    def profile_bigwig_ms(self):
+        """device time of the bigWig kernels of the last profile_bigwig() (up_timings [9])"""
+        t = np.zeros(10, np.float64)
+        _ck(self.L.up_timings(self.ctx, t.ctypes.data, 10))
+        return float(t[9])
 
     def set_profile_capture(self, on):
         _ck(self.L.up_set_profile_capture(self.ctx, int(bool(on))))

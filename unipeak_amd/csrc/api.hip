@@ -30,6 +30,7 @@
 #include "headplace.hip"
 #include "wide.hip"
 #include "proftext.hip"
+#include "bigwig.hip"
 
 namespace upk {
 // the templated K1 / K3 / K4 kernels live in eight translation units, one per
@@ -199,6 +200,23 @@ struct up_ctx {
     Event pt_ev[4];
     double text_ms = 0;
     double text_limit = HUGE_VAL;
+    // up_unit_profile_bigwig (bigwig.hip): the dense float bits, per-workgroup
+    // item counts + the flag, their prefix, items, section records, the bins of
+    // every zoom level, their per-workgroup counts and prefix, the zoom records;
+    // the outputs in pinned host memory (totals: items, -, flag; the zoom prefix
+    // behind them); its kernels' time (up_timings [9])
+    DevBuf<uint32_t> d_bw_val, d_bw_blk, d_bw_zblk;
+    DevBuf<uint64_t> d_bw_off, d_bw_zoff;
+    DevBuf<uint2> d_bw_items;
+    DevBuf<BwSection> d_bw_sec;
+    DevBuf<BwBin> d_bw_bins;
+    DevBuf<uint4> d_bw_zrec;
+    HostBuf<uint2> h_bw_items;
+    HostBuf<BwSection> h_bw_sec;
+    HostBuf<uint4> h_bw_zrec;
+    HostBuf<uint64_t> h_bw_tot;
+    Event bw_ev[4];
+    double bigwig_ms = 0;
     int timing = 2;                  // up_set_timing: 0 wall only, 1 + K1a, 2 every phase
     // passes in flight (up_run_async); slot = sequence % kSlots.  Each slot
     // owns its device buffers and its stream, so a pass's streaming K1a can
@@ -503,6 +521,17 @@ int up_format_g6(double v, char *out, int *n) {
     return UP_OK;
 }
 
+// (float)strtod(printf("%g", v)) by the routine the device runs (fmt_g6.h)
+int up_g6_to_float(double v, float *out, int *ok) {
+    if (!out || !ok) return UP_E_ARG;
+    uint64_t bits;
+    memcpy(&bits, &v, sizeof bits);
+    uint32_t fb = 0;
+    *ok = g6_to_float(bits, &fb) ? 1 : 0;
+    memcpy(out, &fb, sizeof fb);
+    return UP_OK;
+}
+
 int up_open(int hip_device, up_ctx **out) {
     if (!out) return UP_E_ARG;
     int n = 0;
@@ -548,6 +577,7 @@ int up_open(int hip_device, up_ctx **out) {
     }
     for (auto &e : c->ev) HIPCHK(hipEventCreate(&e));
     for (auto &e : c->pt_ev) HIPCHK(hipEventCreate(&e));
+    for (auto &e : c->bw_ev) HIPCHK(hipEventCreate(&e));
     for (auto &ps : c->pass) {
         for (auto &e : ps.ev) HIPCHK(hipEventCreate(&e));
         for (auto &e : ps.hev) HIPCHK(hipEventCreate(&e));
@@ -3626,6 +3656,7 @@ int up_timings(up_ctx *c, double *ms, int n) {
     if (n > 5) ms[5] = c->prof_ms;
     for (int i = 6; i < n && i < 8; ++i) ms[i] = c->head_ms[i - 6];
     if (n > 8) ms[8] = c->text_ms;
+    if (n > 9) ms[9] = c->bigwig_ms;
     return UP_OK;
 }
 
@@ -3773,6 +3804,138 @@ int up_unit_profile_text(up_ctx *c, uint32_t unit, uint64_t first, uint32_t coun
     if (bytes) *text = (const char *)c->h_pt_text.p;
     *n_bytes = bytes;
     *n_lines = lines;
+    return UP_OK;
+}
+
+int up_unit_profile_bigwig(up_ctx *c, uint32_t unit, uint64_t first, uint32_t count, int32_t negate,
+                           uint64_t clip_end, uint32_t reduction0, uint32_t n_levels, uint32_t chrom_id,
+                           const up_bw_item **items, uint64_t *n_items, const up_bw_section **sections,
+                           uint64_t *n_sections, const up_bw_zoom **zoom, uint64_t *n_zoom, int32_t *exact) {
+    static_assert(sizeof(up_bw_item) == sizeof(uint2) && sizeof(up_bw_section) == sizeof(BwSection) &&
+                      sizeof(up_bw_zoom) == 2 * sizeof(uint4) && UP_BW_MAX_LEVELS == kBwMaxLevels,
+                  "the header's records are the kernels'");
+    int r = check_runnable(c, true);
+    if (r) return r;
+    if (busy(c)) return UP_E_STATE;
+    if (!items || !n_items || !sections || !n_sections || !exact || (n_levels && (!zoom || !n_zoom))) return UP_E_ARG;
+    if (n_levels > (uint32_t)kBwMaxLevels || (n_levels && !reduction0)) return UP_E_ARG;
+    if (first < 1 || count == 0 || first + count > 0xffffffffull) return UP_E_ARG;  // (starts and ends are uint32)
+    BwLevels L{};
+    L.n = n_levels;
+    {
+        uint64_t red = reduction0, blk = 0;
+        for (uint32_t z = 0; z < n_levels; ++z, red *= 4) {
+            if (red >= (1ull << 31)) return UP_E_ARG;
+            L.red[z] = (uint32_t)red;
+            L.nbins[z] = (uint32_t)(((uint64_t)count + red - 1) / red);
+            L.blk0[z] = (uint32_t)blk;
+            blk += (L.nbins[z] + kBwZBlock - 1) / kBwZBlock;
+        }
+        L.blk0[n_levels] = (uint32_t)blk;
+        // every bin of every level lies inside the call
+        if (n_levels && (first - 1) % L.red[n_levels - 1]) return UP_E_ARG;
+    }
+    *items = nullptr;
+    *sections = nullptr;
+    *n_items = *n_sections = 0;
+    for (uint32_t z = 0; z < n_levels; ++z) {
+        zoom[z] = nullptr;
+        n_zoom[z] = 0;
+    }
+    *exact = 0;
+    StreamScratch scratch(c->stream);
+    double *d_f = nullptr, *d_r = nullptr;
+    if ((r = profile_dense(c, unit, first, count, scratch, &d_f, &d_r))) return r;
+    const uint32_t nblk = (uint32_t)(((uint64_t)count + kPtBlock - 1) / kPtBlock);
+    const uint32_t nzblk = L.blk0[n_levels];
+    HIPCHK(c->d_bw_val.ensure((size_t)nblk * kPtBlock));
+    HIPCHK(c->d_bw_blk.ensure((size_t)nblk + 1));
+    HIPCHK(c->d_bw_off.ensure((size_t)nblk + 1 + 3));
+    HIPCHK(c->h_bw_tot.ensure(3 + (size_t)nzblk + 1));
+    if (nzblk) {
+        HIPCHK(c->d_bw_bins.ensure((size_t)nzblk * kBwZBlock));
+        HIPCHK(c->d_bw_zblk.ensure(nzblk));
+        HIPCHK(c->d_bw_zoff.ensure((size_t)nzblk + 1 + 3));
+    }
+    uint32_t *blk_cnt = c->d_bw_blk.p, *flag = blk_cnt + nblk;
+    uint64_t *blk_off = c->d_bw_off.p, *totals = blk_off + nblk + 1;
+    uint64_t *zoff = c->d_bw_zoff.p, *ztotals = nzblk ? zoff + nzblk + 1 : nullptr;
+    const int neg = negate != 0;
+    HIPCHK(hipMemsetAsync(flag, 0, sizeof(uint32_t), c->stream));
+    HIPCHK(hipEventRecord(c->bw_ev[0], c->stream));
+    hipLaunchKernelGGL(bigwig_value_kernel, dim3(nblk), dim3(kPtThreads), 0, c->stream, d_f, d_r, first, count, neg,
+                       clip_end, c->text_limit, c->d_bw_val.p, blk_cnt, flag);
+    hipLaunchKernelGGL(proftext_scan_kernel, dim3(1), dim3(kPtThreads), 0, c->stream, blk_cnt, blk_cnt, nblk, flag,
+                       blk_off, totals);
+    for (uint32_t z = 0; z < n_levels; ++z) {
+        BwBin *bins = c->d_bw_bins.p + (size_t)L.blk0[z] * kBwZBlock;
+        const dim3 grid((L.nbins[z] + 255) / 256);
+        if (z == 0)
+            hipLaunchKernelGGL(bigwig_zoom0_kernel, grid, dim3(256), 0, c->stream, c->d_bw_val.p, count, L.red[0],
+                               L.nbins[0], bins);
+        else
+            hipLaunchKernelGGL(bigwig_zoomup_kernel, grid, dim3(256), 0, c->stream,
+                               c->d_bw_bins.p + (size_t)L.blk0[z - 1] * kBwZBlock, L.nbins[z - 1], L.nbins[z], bins);
+    }
+    if (nzblk) {
+        hipLaunchKernelGGL(bigwig_zcount_kernel, dim3(nzblk), dim3(kBwZBlock), 0, c->stream, c->d_bw_bins.p, L,
+                           c->d_bw_zblk.p);
+        hipLaunchKernelGGL(proftext_scan_kernel, dim3(1), dim3(kPtThreads), 0, c->stream, c->d_bw_zblk.p,
+                           c->d_bw_zblk.p, nzblk, flag, zoff, ztotals);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->bw_ev[1], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_bw_tot.p, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (nzblk)
+        HIPCHK(hipMemcpyAsync(c->h_bw_tot.p + 3, zoff, ((size_t)nzblk + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                              c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    profile_dense_time(c);
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, c->bw_ev[0], c->bw_ev[1]);
+    c->bigwig_ms = ms;
+    if (c->h_bw_tot.p[2]) return UP_OK;  // a score that has no exact float here: *exact = 0
+    *exact = 1;
+    const uint64_t n = c->h_bw_tot.p[0];
+    if (!n) return UP_OK;  // no item: no section, no non-empty bin
+    const uint64_t nsec = (n + kBwSection - 1) / kBwSection;
+    const uint64_t *hz = c->h_bw_tot.p + 3;  // the zoom prefix per workgroup of bins
+    const uint64_t nrec = nzblk ? hz[nzblk] : 0;
+    HIPCHK(c->d_bw_items.ensure(n));
+    HIPCHK(c->h_bw_items.ensure(n));
+    HIPCHK(c->d_bw_sec.ensure(nsec));
+    HIPCHK(c->h_bw_sec.ensure(nsec));
+    if (nrec) {
+        HIPCHK(c->d_bw_zrec.ensure(2 * nrec));
+        HIPCHK(c->h_bw_zrec.ensure(2 * nrec));
+    }
+    HIPCHK(hipEventRecord(c->bw_ev[2], c->stream));
+    hipLaunchKernelGGL(bigwig_items_kernel, dim3(nblk), dim3(kPtThreads), 0, c->stream, c->d_bw_val.p, blk_off, first,
+                       c->d_bw_items.p);
+    hipLaunchKernelGGL(bigwig_sections_kernel, dim3((unsigned)nsec), dim3(64), 0, c->stream, c->d_bw_items.p, n,
+                       c->d_bw_sec.p);
+    if (nrec)
+        hipLaunchKernelGGL(bigwig_zwrite_kernel, dim3(nzblk), dim3(kBwZBlock), 0, c->stream, c->d_bw_bins.p, L, zoff,
+                           chrom_id, first, clip_end, c->d_bw_zrec.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->bw_ev[3], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_bw_items.p, c->d_bw_items.p, n * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_bw_sec.p, c->d_bw_sec.p, nsec * sizeof(BwSection), hipMemcpyDeviceToHost, c->stream));
+    if (nrec)
+        HIPCHK(hipMemcpyAsync(c->h_bw_zrec.p, c->d_bw_zrec.p, 2 * nrec * sizeof(uint4), hipMemcpyDeviceToHost,
+                              c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)hipEventElapsedTime(&ms, c->bw_ev[2], c->bw_ev[3]);
+    c->bigwig_ms += ms;
+    *items = (const up_bw_item *)c->h_bw_items.p;
+    *n_items = n;
+    *sections = (const up_bw_section *)c->h_bw_sec.p;
+    *n_sections = nsec;
+    for (uint32_t z = 0; z < n_levels; ++z) {
+        const uint64_t a = hz[L.blk0[z]], b = hz[L.blk0[z + 1]];
+        n_zoom[z] = b - a;
+        if (b > a) zoom[z] = (const up_bw_zoom *)(c->h_bw_zrec.p + 2 * a);
+    }
     return UP_OK;
 }
 

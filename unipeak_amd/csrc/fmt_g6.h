@@ -230,4 +230,48 @@ UPK_HD inline int g6_format(uint64_t bits, char *out) {
     return g6_put(out, D, X, neg);
 }
 
+// ---- the float a reader of the %g text gets: (float)strtod("<%g of v>")
+//
+// The text's value is D * 10^k with k = X - 5.  For |k| <= 22 both D (< 2^20)
+// and 10^|k| (5^22 < 2^52) are exact doubles, so one IEEE multiply (k >= 0) or
+// one IEEE divide (k < 0) returns the double nearest to D * 10^k -- what a
+// correctly rounding strtod returns for that text -- and the conversion to
+// float rounds that double to nearest even, as the reader's cast does (its
+// double rounding is part of the result).  No text is made.  The digit
+// routine's range gives k in [-26, 13]; k < -22 (|v| below about 1e-17) is
+// refused.  Needs a real FP64 multiply / divide: no fast-math, no contraction.
+
+UPK_HD inline double g6_pow10d(int k) {  // 10^k, k = 0..22, each exact
+    constexpr double t[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
+                              1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+    return t[k];
+}
+
+constexpr int kG6FloatMaxK = 22;
+
+// the float (as bits) of the text of (D, X, neg); false: |X - 5| > 22
+UPK_HD inline bool g6_digits_to_float(uint32_t D, int X, bool neg, uint32_t *fbits) {
+    const int k = X - 5;
+    if (k < -kG6FloatMaxK || k > kG6FloatMaxK) return false;
+    const double d = k >= 0 ? (double)D * g6_pow10d(k) : (double)D / g6_pow10d(-k);
+    const float f = (float)d;
+    union {
+        float f;
+        uint32_t u;
+    } c;
+    c.f = neg ? -f : f;
+    *fbits = c.u;
+    return true;
+}
+
+// (float)strtod(printf("%g", v)) of the double with these bits, as the float's
+// bits; false: outside g6_digits' range, or its text is below 1e-17
+UPK_HD inline bool g6_to_float(uint64_t bits, uint32_t *fbits) {
+    uint32_t D;
+    int X;
+    bool neg;
+    if (!g6_digits(bits, &D, &X, &neg)) return false;
+    return g6_digits_to_float(D, X, neg, fbits);
+}
+
 }  // namespace upk

@@ -1,10 +1,12 @@
 // unipeak_amd/host/engine.cpp -- see engine.hpp.
 #include "engine.hpp"
 #include "cli.hpp"
+#include "bbi.hpp"
 
 #include <algorithm>
 #include <unordered_map>
 #include <atomic>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -816,6 +818,340 @@ void write_profile(const PassResult &pr, uint16_t bw, ProfileSink &sink) {
             }
             x = end;
         }
+    }
+}
+
+namespace {
+
+static_assert(sizeof(up_bw_item) == 8 && sizeof(up_bw_zoom) == sizeof(bbi::ZoomRecord),
+              "items and zoom records go to disk as the device wrote them");
+
+// what wigs2bigwigs makes of the -w line of `score`: the text's double, cast
+// to float; the reverse buffer's line carries a '-' in front of the %g text
+float bw_host_value(double score, bool negate) {
+    float f = 0;
+    int ok = 0;
+    if (!(negate && score < 0) && up_g6_to_float(score, &f, &ok) == UP_OK && ok) return negate ? -f : f;
+    char buf[64];
+    std::snprintf(buf, sizeof buf, negate ? "-%g" : "%g", score);
+    return (float)std::strtod(buf, nullptr);
+}
+
+up_bw_section bw_host_section(const up_bw_item *it, size_t n) {
+    up_bw_section s{};
+    s.start = it[0].start;
+    s.end = it[n - 1].start + 1;
+    s.count = (uint32_t)n;
+    s.vmin = s.vmax = it[0].value;
+    for (size_t i = 0; i < n; ++i) {
+        const double v = it[i].value;
+        s.vmin = std::min(s.vmin, it[i].value);
+        s.vmax = std::max(s.vmax, it[i].value);
+        s.sum += v;
+        s.sumsq += v * v;
+    }
+    return s;
+}
+
+// the zoom records of sorted items on the fixed grid, level by level
+void bw_host_zoom(const std::vector<up_bw_item> &items, uint32_t chrom, uint32_t clip_end, uint32_t red0,
+                  uint32_t n_levels, std::vector<std::vector<up_bw_zoom>> &zoom) {
+    uint64_t red = red0;
+    for (uint32_t z = 0; z < n_levels; ++z, red *= 4) {
+        for (size_t i = 0; i < items.size();) {
+            const uint64_t bin = items[i].start / red;
+            up_bw_zoom r{};
+            r.chrom = chrom;
+            r.start = (uint32_t)(bin * red);
+            r.end = (uint32_t)std::min<uint64_t>(bin * red + red, clip_end);
+            r.vmin = r.vmax = items[i].value;
+            double sum = 0, sumsq = 0;
+            for (; i < items.size() && items[i].start / red == bin; ++i) {
+                const double v = items[i].value;
+                r.vmin = std::min(r.vmin, items[i].value);
+                r.vmax = std::max(r.vmax, items[i].value);
+                sum += v;
+                sumsq += v * v;
+                ++r.valid;
+            }
+            r.sum = (float)sum;
+            r.sumsq = (float)sumsq;
+            zoom[z].push_back(r);
+        }
+    }
+}
+
+// one bigWig file being written: data sections are appended as they come,
+// the index and the zoom records wait for the trailer
+struct BwTrack {
+    std::string path;
+    std::FILE *fp = nullptr;
+    uint64_t at = 0;  // file offset
+    uint64_t summary_off = 0, tree_off = 0, data_off = 0;
+    std::vector<std::string> names;  // chromosomes that hold items, in id order
+    std::vector<uint32_t> sizes;
+    std::vector<bbi::Block> blocks;
+    std::vector<std::vector<up_bw_zoom>> zoom;
+    uint32_t red0 = 10, max_raw = 0;
+    uint64_t valid = 0, nitems = 0;
+    double vmin = 0, vmax = 0, sum = 0, sumsq = 0;
+
+    void put(const std::string &s) {
+        if (std::fwrite(s.data(), 1, s.size(), fp) != s.size()) fatal("-W: short write of " + path);
+        at += s.size();
+    }
+    void open(size_t max_chroms, size_t max_key, uint32_t n_levels) {
+        fp = std::fopen(path.c_str(), "wb");
+        if (!fp) fatal("could not write " + path);
+        std::setvbuf(fp, nullptr, _IOFBF, 1 << 22);
+        zoom.assign(n_levels, {});
+        // header, zoom headers, total summary and chromosome tree are written by
+        // finish(); the tree's room is that of every contig the track may hold
+        summary_off = bbi::kHeaderBytes + bbi::kZoomHeaderBytes * n_levels;
+        tree_off = summary_off + bbi::kSummaryBytes;
+        data_off = tree_off + bbi::chrom_tree_bytes(max_chroms, std::max<size_t>(1, max_key));
+        put(std::string(data_off + 8, '\0'));  // + the section count
+    }
+    // the sections of n items of one chunk (sec: their records, or null), compressed on T threads
+    void add_sections(uint32_t chrom, const up_bw_item *it, size_t n, const up_bw_section *sec, unsigned T,
+                      BigWigStats &st) {
+        if (!n) return;
+        const size_t nsec = (n + bbi::kItemsPerSection - 1) / bbi::kItemsPerSection;
+        std::vector<std::string> comp(nsec);
+        std::vector<up_bw_section> rec(nsec);
+        std::atomic<size_t> next{0};
+        std::atomic<bool> failed{false};
+        auto work = [&] {
+            std::string raw;
+            for (size_t s; (s = next.fetch_add(1)) < nsec;) {
+                const up_bw_item *a = it + s * bbi::kItemsPerSection;
+                const size_t k = std::min<size_t>(bbi::kItemsPerSection, n - s * bbi::kItemsPerSection);
+                rec[s] = sec ? sec[s] : bw_host_section(a, k);
+                raw.clear();
+                bbi::put_section_header(raw, chrom, rec[s].start, rec[s].end, 1, (uint16_t)k);
+                raw.append((const char *)a, k * sizeof(up_bw_item));
+                if (!bbi::deflate6(raw.data(), raw.size(), comp[s])) failed = true;
+            }
+        };
+        const auto t0 = std::chrono::steady_clock::now();
+        const unsigned nt = (unsigned)std::min<size_t>(T, nsec);
+        if (nt <= 1) {
+            work();
+        } else {
+            std::vector<std::thread> pool;
+            for (unsigned t = 0; t < nt; ++t) pool.emplace_back(work);
+            for (auto &th : pool) th.join();
+        }
+        st.compress_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (failed) fatal("-W: compression failed");
+        for (size_t s = 0; s < nsec; ++s) {
+            const up_bw_section &r = rec[s];
+            max_raw = std::max<uint32_t>(max_raw, (uint32_t)(bbi::kSectionHeaderBytes + r.count * sizeof(up_bw_item)));
+            blocks.push_back(bbi::Block{chrom, r.start, r.end, at, comp[s].size()});
+            put(comp[s]);
+            vmin = valid ? std::min<double>(vmin, r.vmin) : r.vmin;
+            vmax = valid ? std::max<double>(vmax, r.vmax) : r.vmax;
+            valid += r.count;
+            sum += r.sum;
+            sumsq += r.sumsq;
+        }
+        nitems += n;
+        st.sections += nsec;
+    }
+    void finish(unsigned T, BigWigStats &st) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!nitems) {  // no line, no track header in the -w file: wigs2bigwigs writes no file
+            std::fclose(fp);
+            fp = nullptr;
+            std::remove(path.c_str());
+            return;
+        }
+        const uint64_t index_off = at;
+        std::string f;
+        bbi::write_rtree(f, blocks, bbi::kRtreeBlock, bbi::kItemsPerSection, at);
+        put(f);
+        // a level is kept while it has fewer records than the one before it
+        // (and than the items): wigs2bigwigs's rule
+        std::vector<bbi::ZoomPlace> places;
+        uint64_t prev = nitems, red = red0;
+        for (size_t z = 0; z < zoom.size(); ++z, red *= 4) {
+            if (zoom[z].empty() || zoom[z].size() >= prev) break;
+            prev = zoom[z].size();
+            f.clear();
+            bbi::ZoomPlace place{};
+            if (!bbi::write_zoom_level(f, (const bbi::ZoomRecord *)zoom[z].data(), zoom[z].size(), (uint32_t)red,
+                                       max_raw, place, at, T))
+                fatal("-W: compression failed");
+            put(f);
+            places.push_back(place);
+        }
+        f.clear();
+        bbi::put32(f, bbi::kMagic);
+        put(f);
+        std::string head = bbi::header_bytes(tree_off, data_off, index_off, summary_off, max_raw, places);
+        head.resize(summary_off, '\0');
+        head += bbi::summary_bytes(valid, vmin, vmax, sum, sumsq);
+        bbi::write_chrom_tree(head, names, sizes);
+        if (head.size() > data_off) fatal("-W: the chromosome tree outgrew its room");
+        head.resize(data_off, '\0');
+        bbi::put64(head, blocks.size());
+        if (std::fseek(fp, 0, SEEK_SET) != 0 || std::fwrite(head.data(), 1, head.size(), fp) != head.size() ||
+            std::fclose(fp) != 0)
+            fatal("-W: could not finish " + path);
+        fp = nullptr;
+        st.trailer_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+};
+
+}  // namespace
+
+void write_profile_bigwig(const PassResult &pr, uint16_t bw, BigWigSink &sink) {
+    (void)bw;
+    const ContigTable &ct = *sink.ct;
+    BigWigStats &st = sink.stats;
+    std::vector<std::pair<up_ctx *, uint32_t>> where(pr.units.size(), {nullptr, 0});
+    for (const DeviceJob &j : g_jobs)
+        for (size_t k = 0; k < j.dev_unit.size(); ++k) where[j.dev_unit[k]] = {j.ctx, (uint32_t)k};
+    // a chunk is a multiple of the top level's bin, so no bin of any level
+    // straddles two calls: 10 * 4^9 positions, ten levels from 10 bases up
+    const uint32_t red0 = 10;
+    uint64_t chunk = (uint64_t)red0 << 18;
+    uint32_t n_levels = UP_BW_MAX_LEVELS;
+    if (const char *e = std::getenv("UNIPEAK_BIGWIG_CHUNK")) {  // tests: several chunks of a short contig
+        const unsigned long long v = std::strtoull(e, nullptr, 10);
+        if (v >= 1 && v <= (1ull << 30)) {
+            chunk = v;
+            n_levels = 0;  // as many levels as keep the chunk a multiple of the top bin
+            for (uint64_t r = red0; n_levels < UP_BW_MAX_LEVELS && chunk % r == 0; r *= 4) ++n_levels;
+        }
+    }
+    const unsigned T = std::min(16u, ingest_threads());
+    // the units of each track, by contig: one unit per contig
+    const int ntracks = sink.directional ? 2 : 1;
+    std::vector<std::vector<uint32_t>> units(ntracks);
+    for (int b = 0; b < ntracks; ++b) {
+        std::vector<int64_t> seen(ct.size(), -1);
+        for (uint32_t k = 0; k < pr.units.size(); ++k) {
+            const UnitBuild &u = pr.units[k];
+            if (u.buffer != b) continue;
+            if (seen[u.contig] >= 0)
+                fatal("-W: contig " + ct.name(u.contig) + " reaches the " +
+                      (sink.directional ? (b ? "reverse" : "forward") : "only") +
+                      " track from more than one unit (its records are interleaved with another contig's); "
+                      "a bigWig cannot hold overlapping items");
+            seen[u.contig] = k;
+            units[b].push_back(k);
+        }
+        std::stable_sort(units[b].begin(), units[b].end(), [&](uint32_t x, uint32_t y) {
+            return ct.name(pr.units[x].contig) < ct.name(pr.units[y].contig);
+        });
+    }
+    for (int b = 0; b < ntracks; ++b) {
+        BwTrack t;
+        t.path = sink.root + (sink.directional ? (b ? "-" : "+") : "") + ".bw";
+        t.red0 = red0;
+        if (units[b].size() > 65535) fatal("-W: too many chromosomes for one B+ tree node");
+        size_t max_key = 1;
+        for (uint32_t k : units[b]) max_key = std::max(max_key, ct.name(pr.units[k].contig).size());
+        t.open(units[b].size(), max_key, n_levels);
+        const bool negate = sink.directional && b != 0;
+        for (uint32_t k : units[b]) {
+            const UnitBuild &u = pr.units[k];
+            up_ctx *ctx = where[k].first;
+            const uint32_t du = where[k].second;
+            const uint32_t chrom = (uint32_t)t.names.size();  // its id once it holds an item
+            const uint64_t before = t.nitems;
+            std::vector<size_t> z0(n_levels);  // where the unit's zoom records start
+            for (uint32_t z = 0; z < n_levels; ++z) z0[z] = t.zoom[z].size();
+            // replayed entries: converted on the host, the unit's first sections
+            uint32_t resync = 0;
+            uint64_t n = 0;
+            int rc = up_unit_replay_profile(ctx, du, &resync, &n, nullptr, nullptr, nullptr, 0);
+            if (rc != UP_OK) fatal(std::string("up_unit_replay_profile: ") + up_strerror(rc));
+            std::vector<up_bw_item> head;  // items the host zoom sees: replayed, then the resync chunk's
+            if (n) {
+                std::vector<uint32_t> ev(n), pos(n);
+                std::vector<double> score(n);
+                if ((rc = up_unit_replay_profile(ctx, du, &resync, &n, ev.data(), pos.data(), score.data(), n)) != UP_OK)
+                    fatal(std::string("up_unit_replay_profile: ") + up_strerror(rc));
+                for (uint64_t i = 0; i < n; ++i) {
+                    if (score[i] == 0 || pos[i] > u.len) continue;  // no line; -clip
+                    if (pos[i] == 0) fatal("-W: a replayed entry at position 0");
+                    head.push_back(up_bw_item{pos[i] - 1, bw_host_value(score[i], negate)});
+                }
+                std::stable_sort(head.begin(), head.end(),
+                                 [](const up_bw_item &x, const up_bw_item &y) { return x.start < y.start; });
+                st.host_items += head.size();
+                t.add_sections(chrom, head.data(), head.size(), nullptr, T, st);
+            }
+            const bool replayed_part = resync != 0;
+            if (resync != UP_FLUSH_EVENT) {
+                const uint64_t x0 = resync ? resync : 1;  // dense from the resync point on
+                for (uint64_t first = ((x0 - 1) / chunk) * chunk + 1; first <= u.len; first += chunk) {
+                    const uint32_t count = (uint32_t)std::min<uint64_t>(chunk, (uint64_t)u.len - first + 1);
+                    ++st.chunks;
+                    const up_bw_item *items = nullptr;
+                    const up_bw_section *secs = nullptr;
+                    const up_bw_zoom *zp[UP_BW_MAX_LEVELS] = {nullptr};
+                    uint64_t ni = 0, ns = 0, zn[UP_BW_MAX_LEVELS] = {0};
+                    int32_t exact = 0;
+                    rc = up_unit_profile_bigwig(ctx, du, first, count, negate, u.len, red0, n_levels, chrom, &items,
+                                                &ni, &secs, &ns, zp, zn, &exact);
+                    if (rc != UP_OK) fatal(std::string("up_unit_profile_bigwig: ") + up_strerror(rc));
+                    double ms[10] = {0};
+                    if (up_timings(ctx, ms, 10) == UP_OK) {
+                        st.dense_ms += ms[5];
+                        st.bigwig_ms += ms[9];
+                    }
+                    const bool cut = first < x0;  // the chunk that holds resync: positions below it are dropped
+                    if (exact && !cut) {
+                        st.device_items += ni;
+                        t.add_sections(chrom, items, ni, secs, T, st);
+                        for (uint32_t z = 0; z < n_levels; ++z) t.zoom[z].insert(t.zoom[z].end(), zp[z], zp[z] + zn[z]);
+                        continue;
+                    }
+                    std::vector<up_bw_item> own;
+                    if (exact) {
+                        const up_bw_item *a = std::lower_bound(
+                            items, items + ni, (uint32_t)(x0 - 1),
+                            [](const up_bw_item &x, uint32_t s) { return x.start < s; });
+                        own.assign(a, items + ni);
+                        st.device_items += own.size();
+                    } else {  // converted on the host from the scores
+                        ++st.fallback_chunks;
+                        std::vector<double> f(count, 0.0), r(count, 0.0);
+                        rc = up_unit_profile_range(ctx, du, first, count, f.data(), r.data());
+                        if (rc != UP_OK) fatal(std::string("up_unit_profile_range: ") + up_strerror(rc));
+                        if (up_timings(ctx, ms, 6) == UP_OK) st.dense_ms += ms[5];
+                        for (uint64_t i = (cut ? x0 - first : 0); i < count; ++i) {
+                            const double s = f[i] + r[i];
+                            if (s != 0) own.push_back(up_bw_item{(uint32_t)(first + i - 1), bw_host_value(s, negate)});
+                        }
+                        st.host_items += own.size();
+                    }
+                    t.add_sections(chrom, own.data(), own.size(), nullptr, T, st);
+                    if (cut) {  // its bins are summarised with the replayed part's, below
+                        head.insert(head.end(), own.begin(), own.end());
+                    } else {
+                        bw_host_zoom(own, chrom, u.len, red0, n_levels, t.zoom);
+                    }
+                }
+            }
+            if (replayed_part) {
+                // (the cut chunk's zoom has to come before the later chunks': levels are in start order)
+                std::vector<std::vector<up_bw_zoom>> hz(n_levels);
+                bw_host_zoom(head, chrom, u.len, red0, n_levels, hz);
+                for (uint32_t z = 0; z < n_levels; ++z) {
+                    auto &dst = t.zoom[z];
+                    dst.insert(dst.begin() + (std::ptrdiff_t)z0[z], hz[z].begin(), hz[z].end());
+                }
+            }
+            if (t.nitems != before) {
+                t.names.push_back(ct.name(u.contig));
+                t.sizes.push_back(u.len);
+            }
+        }
+        t.finish(T, st);
     }
 }
 

@@ -121,6 +121,33 @@ struct ProfileSink {
 };
 void write_profile(const PassResult &pr, uint16_t bw, ProfileSink &sink);
 
+// -W: the same profile as bigWig, one file per track -- <root>+.bw and
+// <root>-.bw for a directional run, <root>.bw otherwise, the names
+// wigs2bigwigs derives from <root>.wig -- holding what wigs2bigwigs makes of the
+// -w file: items (pos - 1, (float)strtod of the %g text) clipped at the contig's
+// size, chromosome ids in name order.  Every unit is visited in chunks; the
+// device produces a chunk's items, section records and zoom records
+// (up_unit_profile_bigwig), the host compresses the sections on a pool of at
+// most 16 threads and appends them to the file.  Only the block index and the
+// zoom records stay in memory until the trailer (R-tree, zoom levels, header).
+// Replayed entries (head units, units replayed whole) and chunks the device
+// refuses are converted on the host.  A contig that reaches one track from
+// more than one unit (interleaved input) ends the run with an error.
+struct BigWigStats {
+    uint64_t device_items = 0, host_items = 0, chunks = 0, fallback_chunks = 0, sections = 0;
+    double bigwig_ms = 0, dense_ms = 0;
+    double compress_s = 0;  // wall time in the data sections' compression
+    double trailer_s = 0;   // R-tree, zoom levels (compressed on the same pool), header
+};
+
+struct BigWigSink {
+    std::string root;
+    const ContigTable *ct = nullptr;
+    bool directional = true;
+    BigWigStats stats;
+};
+void write_profile_bigwig(const PassResult &pr, uint16_t bw, BigWigSink &sink);
+
 void release_devices();
 
 }  // namespace unipeak

@@ -27,7 +27,7 @@ int main(int argc, char **argv) {
                   {"l", "length", false, false},        {"s", "shift", false, false},
                   {"p", "prob", false, false},          {"e", "exclude", false, false},
                   {"f", "peaks", true, false},          {"o", "out", false, true},
-                  {"c", "contig", false, true}});
+                  {"c", "contig", false, true},         {"W", "bigwig", false, false}});
     ap.parse(argc, argv);
     PhaseTimer timer;
     const std::vector<std::string> files = ap.files();
@@ -38,6 +38,7 @@ int main(int argc, char **argv) {
     const bool quiet = ap.on("q");
     const bool directional = !ap.on("D");
     const std::string profile = ap.str("w");
+    const std::string bigwig_root = ap.str("W");  // the profile as <root>[+-].bw, with or without -w
     uint32_t mappable = (uint32_t)ap.uint("m", 0, 0xFFFFFFFFull);
     double hit_thr = ap.dbl("t", 10);
     bool out_corrs = ap.on("y");
@@ -221,7 +222,7 @@ int main(int argc, char **argv) {
     ep.control = control;
     ep.coeffs = coeffs;
     ep.ngpus = env_gpus();
-    ep.profile = prof.fp != nullptr;
+    ep.profile = prof.fp != nullptr || !bigwig_root.empty();
     run_units(ep, pr);
     timer.mark("gpu");
     if (prof.fp) {
@@ -235,6 +236,23 @@ int main(int argc, char **argv) {
                          (unsigned long long)prof.stats.device_bytes, (unsigned long long)prof.stats.device_lines,
                          (unsigned long long)prof.stats.host_lines, (unsigned long long)prof.stats.fallback_chunks,
                          (unsigned long long)prof.stats.chunks, prof.stats.text_ms, prof.stats.dense_ms);
+    }
+
+    if (!bigwig_root.empty()) {
+        BigWigSink bws;
+        bws.root = bigwig_root;
+        bws.ct = &ct;
+        bws.directional = directional;
+        write_profile_bigwig(pr, bw, bws);
+        timer.mark("bigwig");
+        if (const char *e = std::getenv("UNIPEAK_TIMING"); e && *e && *e != '0')
+            std::fprintf(stderr,
+                         "[timing] bigwig: device %llu items, host %llu items, fallback chunks %llu of %llu, "
+                         "sections %llu, kernels bigwig %.3f ms dense %.3f ms, compress %.3f s, trailer %.3f s\n",
+                         (unsigned long long)bws.stats.device_items, (unsigned long long)bws.stats.host_items,
+                         (unsigned long long)bws.stats.fallback_chunks, (unsigned long long)bws.stats.chunks,
+                         (unsigned long long)bws.stats.sections, bws.stats.bigwig_ms, bws.stats.dense_ms,
+                         bws.stats.compress_s, bws.stats.trailer_s);
     }
 
     // emission in the reference's order (Q2-Q4); Q3 drops final-flush regions

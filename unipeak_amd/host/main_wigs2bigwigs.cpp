@@ -3,8 +3,11 @@
 // bigWig file per track, with the track headers to load them printed on
 // stdout.  The script pipes each track into UCSC wigToBigWig -clip; this
 // writes the bigWig itself (BBI version 4: chromosome B+ tree, zlib-compressed
-// varStep sections of up to 1024 items, R-tree index, and zoom levels as
-// wigToBigWig builds them), so the pipeline needs no external tool.
+// varStep sections of up to 1024 items, R-tree index, and zoom levels whose
+// records follow wigToBigWig's summary rule; which levels are written is this
+// writer's own choice, and parity with wigToBigWig's is not pinned), so the
+// pipeline needs no external tool.  The BBI pieces are host/bbi.{hpp,cpp},
+// shared with regions -W.
 //
 // Script behaviour kept (extras/wigs2bigwigs.pl:42-75): output root = input
 // name minus /.gz$/ or /.bz2$/ then /.wig$/; '#' lines skipped; a track line
@@ -17,6 +20,8 @@
 // they start past it); chromosomes must be in the sizes file.
 #include <zlib.h>
 
+#include "bbi.hpp"
+
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -28,6 +33,13 @@
 #include <vector>
 
 namespace {
+
+using namespace unipeak;
+using bbi::Block;
+using bbi::put32;
+using bbi::put64;
+using bbi::putf;
+using bbi::set64;
 
 [[noreturn]] void die(const std::string &m) {
     std::cerr << m;
@@ -43,104 +55,6 @@ struct Track {
     std::string out;                              // output file
     std::map<std::string, std::vector<Item>> by;  // chromosome -> items
 };
-
-void put32(std::string &b, uint32_t v) { b.append((const char *)&v, 4); }
-void put64(std::string &b, uint64_t v) { b.append((const char *)&v, 8); }
-void put16(std::string &b, uint16_t v) { b.append((const char *)&v, 2); }
-void putf(std::string &b, float v) { b.append((const char *)&v, 4); }
-void putd(std::string &b, double v) { b.append((const char *)&v, 8); }
-void set64(std::string &b, size_t at, uint64_t v) { std::memcpy(&b[at], &v, 8); }
-
-struct Block {  // one compressed section and its extent
-    uint32_t chrom, start, end;
-    uint64_t offset, size;
-};
-
-// R-tree (cirTree) over the blocks, bottom-up, blockSize children per node
-void write_rtree(std::string &f, const std::vector<Block> &blocks, uint32_t block_size, uint32_t items_per_slot) {
-    const uint64_t data_end = f.size();
-    put32(f, 0x2468ACE0u);
-    put32(f, block_size);
-    put64(f, blocks.size());
-    put32(f, blocks.empty() ? 0 : blocks.front().chrom);
-    put32(f, blocks.empty() ? 0 : blocks.front().start);
-    put32(f, blocks.empty() ? 0 : blocks.back().chrom);
-    uint32_t end_base = 0;
-    for (const Block &b : blocks)
-        if (b.chrom == blocks.back().chrom) end_base = std::max(end_base, b.end);
-    put32(f, end_base);
-    put64(f, data_end);
-    put32(f, items_per_slot);
-    put32(f, 0);
-    // levels: level 0 = leaves over the blocks; each parent level groups
-    // block_size nodes.  Nodes are written root first.
-    struct Node {
-        uint32_t c0, s0, c1, s1;
-        size_t first, count;  // children in the level below
-    };
-    std::vector<std::vector<Node>> levels;
-    {
-        std::vector<Node> leaves;
-        for (size_t i = 0; i < blocks.size(); i += block_size) {
-            const size_t n = std::min<size_t>(block_size, blocks.size() - i);
-            Node nd{blocks[i].chrom, blocks[i].start, blocks[i + n - 1].chrom, 0, i, n};
-            for (size_t k = i; k < i + n; ++k)
-                if (blocks[k].chrom == nd.c1) nd.s1 = std::max(nd.s1, blocks[k].end);
-            leaves.push_back(nd);
-        }
-        if (leaves.empty()) leaves.push_back(Node{0, 0, 0, 0, 0, 0});
-        levels.push_back(leaves);
-    }
-    while (levels.back().size() > 1) {
-        const std::vector<Node> &below = levels.back();
-        std::vector<Node> up;
-        for (size_t i = 0; i < below.size(); i += block_size) {
-            const size_t n = std::min<size_t>(block_size, below.size() - i);
-            Node nd{below[i].c0, below[i].s0, below[i + n - 1].c1, 0, i, n};
-            for (size_t k = i; k < i + n; ++k)
-                if (below[k].c1 == nd.c1) nd.s1 = std::max(nd.s1, below[k].s1);
-            up.push_back(nd);
-        }
-        levels.push_back(up);
-    }
-    // offsets: root level first, then downwards
-    const size_t L = levels.size();
-    std::vector<std::vector<uint64_t>> off(L);
-    uint64_t at = f.size();
-    for (size_t l = L; l-- > 0;) {
-        const bool leaf = l == 0;
-        for (const Node &nd : levels[l]) {
-            off[l].push_back(at);
-            at += 4 + nd.count * (leaf ? 32 : 24);
-        }
-    }
-    for (size_t l = L; l-- > 0;) {
-        const bool leaf = l == 0;
-        for (const Node &nd : levels[l]) {
-            f.push_back(leaf ? 1 : 0);
-            f.push_back(0);
-            put16(f, (uint16_t)nd.count);
-            for (size_t k = nd.first; k < nd.first + nd.count; ++k) {
-                if (leaf) {
-                    const Block &b = blocks[k];
-                    put32(f, b.chrom);
-                    put32(f, b.start);
-                    put32(f, b.chrom);
-                    put32(f, b.end);
-                    put64(f, b.offset);
-                    put64(f, b.size);
-                } else {
-                    const Node &c = levels[l - 1][k];
-                    put32(f, c.c0);
-                    put32(f, c.s0);
-                    put32(f, c.c1);
-                    put32(f, c.s1);
-                    put64(f, off[l - 1][k]);
-                }
-            }
-        }
-    }
-}
 
 // one zoom-level record (bbiSummaryOnDisk): the bases of one bin that hold
 // data, and their value statistics
@@ -192,8 +106,6 @@ void write_bigwig(const Track &t, const std::map<std::string, uint32_t> &sizes) 
     std::vector<std::string> names;
     for (const auto &kv : t.by) names.push_back(kv.first);
     std::sort(names.begin(), names.end());
-    size_t key_size = 1;
-    for (const std::string &n : names) key_size = std::max(key_size, n.size());
     std::vector<std::vector<Item>> sorted(names.size());
     std::vector<uint32_t> csize(names.size());
     uint64_t nitems = 0, bases = 0;
@@ -205,9 +117,12 @@ void write_bigwig(const Track &t, const std::map<std::string, uint32_t> &sizes) 
         for (const Item &it : sorted[ci]) bases += it.end - it.start;
         nitems += sorted[ci].size();
     }
-    // zoom levels (wigToBigWig: up to 10, each 4x the previous, the first
-    // 10x the average item span): a level is kept while it has fewer
-    // summaries than the level before it (and than the items themselves)
+    // zoom levels: up to 10, each 4x the previous, the first 10x the average
+    // item span; a level is kept while it has fewer summaries than the level
+    // before it (and than the items themselves).  This choice of levels is
+    // this writer's own: wigToBigWig's is not pinned by any test here (the
+    // tool is not available to compare with), only each level's records are
+    // built by its rule (summarise)
     std::vector<std::pair<uint32_t, std::vector<Summary>>> zooms;
     if (nitems) {
         uint64_t red = std::max<uint64_t>(1, (bases + nitems / 2) / nitems) * 10;
@@ -219,28 +134,14 @@ void write_bigwig(const Track &t, const std::map<std::string, uint32_t> &sizes) 
             zooms.emplace_back((uint32_t)red, std::move(sm));
         }
     }
-    std::string f(64 + 24 * zooms.size(), '\0');  // header and zoom headers, patched at the end
+    // header and zoom headers, patched at the end
+    std::string f(bbi::kHeaderBytes + bbi::kZoomHeaderBytes * zooms.size(), '\0');
     const uint64_t summary_off = f.size();
-    f.append(40, '\0');
+    f.append(bbi::kSummaryBytes, '\0');
     const uint64_t tree_off = f.size();
     const uint32_t nchrom = (uint32_t)names.size();
     if (nchrom > 65535) die("error: too many chromosomes for one B+ tree node\n");
-    put32(f, 0x78CA8C91u);
-    put32(f, std::max<uint32_t>(nchrom, 1));
-    put32(f, (uint32_t)key_size);
-    put32(f, 8);
-    put64(f, nchrom);
-    put64(f, 0);
-    f.push_back(1);
-    f.push_back(0);
-    put16(f, (uint16_t)nchrom);
-    for (uint32_t i = 0; i < nchrom; ++i) {
-        std::string k = names[i];
-        k.resize(key_size, '\0');
-        f += k;
-        put32(f, i);
-        put32(f, sizes.at(names[i]));
-    }
+    bbi::write_chrom_tree(f, names, csize);
     // data: varStep sections of up to 1024 items, span 1 per section run
     const uint64_t data_off = f.size();
     put64(f, 0);  // section count, patched
@@ -256,14 +157,7 @@ void write_bigwig(const Track &t, const std::map<std::string, uint32_t> &sizes) 
             size_t j = i;
             while (j < items.size() && j - i < 1024 && items[j].end - items[j].start == span) ++j;
             std::string raw;
-            put32(raw, ci);
-            put32(raw, items[i].start);
-            put32(raw, items[j - 1].end);
-            put32(raw, 0);
-            put32(raw, span);
-            raw.push_back(2);  // varStep
-            raw.push_back(0);
-            put16(raw, (uint16_t)(j - i));
+            bbi::put_section_header(raw, ci, items[i].start, items[j - 1].end, span, (uint16_t)(j - i));
             for (size_t k = i; k < j; ++k) {
                 put32(raw, items[k].start);
                 putf(raw, items[k].value);
@@ -275,84 +169,36 @@ void write_bigwig(const Track &t, const std::map<std::string, uint32_t> &sizes) 
                 vsq += v * v * span;
             }
             max_raw = std::max<uint32_t>(max_raw, (uint32_t)raw.size());
-            uLongf clen = compressBound(raw.size());
-            std::string comp(clen, '\0');
-            if (compress2((Bytef *)&comp[0], &clen, (const Bytef *)raw.data(), raw.size(), 6) != Z_OK)
-                die("error: compression failed\n");
-            comp.resize(clen);
-            blocks.push_back(Block{ci, items[i].start, items[j - 1].end, f.size(), clen});
+            std::string comp;
+            if (!bbi::deflate6(raw.data(), raw.size(), comp)) die("error: compression failed\n");
+            blocks.push_back(Block{ci, items[i].start, items[j - 1].end, f.size(), comp.size()});
             f += comp;
             i = j;
         }
     }
     set64(f, data_off, blocks.size());
     const uint64_t index_off = f.size();
-    write_rtree(f, blocks, 256, 1024);
+    bbi::write_rtree(f, blocks, bbi::kRtreeBlock, bbi::kItemsPerSection);
     // zoom levels: per level a uint32 record count, zlib blocks of up to 1024
     // summaries (one chromosome each), their R-tree
-    std::vector<std::pair<uint64_t, uint64_t>> zoff;  // data, index
+    std::vector<bbi::ZoomPlace> zoff;
     for (const auto &zl : zooms) {
-        const std::vector<Summary> &sm = zl.second;
-        const uint64_t zdata = f.size();
-        put32(f, (uint32_t)sm.size());
-        std::vector<Block> zb;
-        for (size_t i = 0; i < sm.size();) {
-            size_t j = i;
-            while (j < sm.size() && j - i < 1024 && sm[j].chrom == sm[i].chrom) ++j;
-            std::string raw;
-            for (size_t k = i; k < j; ++k) {
-                put32(raw, sm[k].chrom);
-                put32(raw, sm[k].start);
-                put32(raw, sm[k].end);
-                put32(raw, sm[k].valid);
-                putf(raw, sm[k].vmin);
-                putf(raw, sm[k].vmax);
-                putf(raw, (float)sm[k].sum);
-                putf(raw, (float)sm[k].sumsq);
-            }
-            max_raw = std::max<uint32_t>(max_raw, (uint32_t)raw.size());
-            uLongf clen = compressBound(raw.size());
-            std::string comp(clen, '\0');
-            if (compress2((Bytef *)&comp[0], &clen, (const Bytef *)raw.data(), raw.size(), 6) != Z_OK)
-                die("error: compression failed\n");
-            comp.resize(clen);
-            zb.push_back(Block{sm[i].chrom, sm[i].start, sm[j - 1].end, f.size(), clen});
-            f += comp;
-            i = j;
-        }
-        const uint64_t zindex = f.size();
-        write_rtree(f, zb, 256, 1024);
-        zoff.emplace_back(zdata, zindex);
+        std::vector<bbi::ZoomRecord> rec;
+        rec.reserve(zl.second.size());
+        for (const Summary &sm : zl.second)
+            rec.push_back(bbi::ZoomRecord{sm.chrom, sm.start, sm.end, sm.valid, sm.vmin, sm.vmax, (float)sm.sum,
+                                          (float)sm.sumsq});
+        bbi::ZoomPlace place{};
+        if (!bbi::write_zoom_level(f, rec.data(), rec.size(), zl.first, max_raw, place))
+            die("error: compression failed\n");
+        zoff.push_back(place);
     }
-    put32(f, 0x888FFC26u);  // trailing magic
+    put32(f, bbi::kMagic);  // trailing magic
     // header, zoom headers and total summary
-    std::string h;
-    put32(h, 0x888FFC26u);
-    put16(h, 4);
-    put16(h, (uint16_t)zooms.size());
-    put64(h, tree_off);
-    put64(h, data_off);
-    put64(h, index_off);
-    put16(h, 0);
-    put16(h, 0);
-    put64(h, 0);
-    put64(h, summary_off);
-    put32(h, max_raw);
-    put64(h, 0);
-    for (size_t z = 0; z < zooms.size(); ++z) {
-        put32(h, zooms[z].first);
-        put32(h, 0);
-        put64(h, zoff[z].first);
-        put64(h, zoff[z].second);
-    }
+    const std::string h = bbi::header_bytes(tree_off, data_off, index_off, summary_off, max_raw, zoff);
     std::memcpy(&f[0], h.data(), h.size());
-    std::string s;
-    put64(s, valid);
-    putd(s, valid ? vmin : 0);
-    putd(s, valid ? vmax : 0);
-    putd(s, vsum);
-    putd(s, vsq);
-    std::memcpy(&f[summary_off], s.data(), 40);
+    const std::string sb = bbi::summary_bytes(valid, vmin, vmax, vsum, vsq);
+    std::memcpy(&f[summary_off], sb.data(), bbi::kSummaryBytes);
     FILE *fp = std::fopen(t.out.c_str(), "wb");
     if (!fp) die("error: " + t.out + ": could not write\n");
     std::fwrite(f.data(), 1, f.size(), fp);
