@@ -585,6 +585,44 @@ int up_cm_collect(up_cm *h, int nondir, uint64_t *n, uint32_t *contig, uint32_t 
 /* device time in ms: [0] every up_cm_add kernel so far, [1] the last collect */
 int up_cm_timings(up_cm *h, double *ms, int n);
 
+/* ---- deflate: a DEFLATE (RFC 1951) encoder on the GPU ----------------------
+ * One workgroup encodes one independent block of at most up_dfl_block() input
+ * bytes: LZ77 inside the block (distance <= 32,768, length 3..258, every
+ * candidate verified), one dynamic-Huffman block, or stored blocks where that
+ * is not smaller.  A block's output is a function of its input bytes alone.
+ *
+ * up_dfl_stream: src is host memory; *out points at pinned host memory of the
+ * handle, valid until its next call.  The output is raw DEFLATE, byte-aligned
+ * at the end (every block closes with an empty stored block, like a sync
+ * flush), no block marked final: put a gzip or zlib header in front,
+ * concatenate the outputs of several calls, close with an empty final block
+ * (03 00) and the trailer.  *crc32 = CRC-32 of src[0, n).  n = 0 gives zero
+ * bytes.  *n_out <= up_dfl_bound(n).
+ *
+ * up_dfl_segments: segment i = src[seg_off[i], seg_off[i + 1]), at most
+ * 65,536 bytes (UP_E_ARG otherwise), becomes one complete zlib stream
+ * (RFC 1950: header, last block final, Adler-32) at
+ * out[out_off[i], out_off[i + 1]).  Lengths 0 and 1 are valid.
+ *
+ * up_dfl_code_lengths: the length-limited Huffman code lengths the kernel
+ * builds, on the host: len[s] = 0 for freq[s] = 0, else 1..max_len with a
+ * Kraft sum of exactly 1 when two or more symbols are used (one used symbol
+ * gets length 1).  n <= 288, max_len <= 15, sum of freq < 2^32, and at most
+ * 2^max_len used symbols (UP_E_ARG otherwise: no such code exists). */
+typedef struct up_dfl up_dfl;
+int up_dfl_open(int device, up_dfl **h);
+void up_dfl_close(up_dfl *h);
+uint32_t up_dfl_block(void);       /* input bytes per independent block */
+uint64_t up_dfl_bound(uint64_t n); /* upper bound of up_dfl_stream's output for n input bytes */
+int up_dfl_stream(up_dfl *h, const void *src, uint64_t n, const void **out, uint64_t *n_out,
+                  uint32_t *crc32);
+int up_dfl_segments(up_dfl *h, const void *src, const uint64_t *seg_off /* n_seg + 1 */,
+                    uint32_t n_seg, const void **out, uint64_t *out_off /* n_seg + 1 */);
+/* totals since open: [0] device ms of the encode and compact kernels,
+ * [1] input bytes, [2] output bytes, [3] calls */
+int up_dfl_timings(up_dfl *h, double *v, int n);
+int up_dfl_code_lengths(const uint32_t *freq, uint32_t n, uint32_t max_len, uint8_t *len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,9 +16,9 @@ flt = args[0] if args else ""
 base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c",
         "-ffp-contract=off", "-I", f"{ROOT}/include", "-o", "/dev/null",
         "-Rpass-analysis=kernel-resource-usage"] + extra
-# api.hip (non-templated kernels) and the per-NH units (templated kernels)
+# api.hip (non-templated kernels), deflate.hip and the per-NH units (templated kernels)
 nhs = [int(x) for x in __import__("os").environ.get("NH", "1,2").split(",")]
-cmds = [base + [f"{ROOT}/unipeak_amd/csrc/api.hip"]] + [
+cmds = [base + [f"{ROOT}/unipeak_amd/csrc/api.hip"], base + [f"{ROOT}/unipeak_amd/csrc/deflate.hip"]] + [
     base + [f"-DUPK_NH_TU={k}", f"{ROOT}/unipeak_amd/csrc/nh_tu.hip"] for k in nhs]
 out = "\n".join(subprocess.run(c, capture_output=True, text=True).stderr for c in cmds)
 rows, cur = [], None
@@ -39,7 +39,7 @@ for line in out.splitlines():
 for r in rows:
     n = r["name"]
     d = subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip()
-    d = re.sub(r"\(.*", "", d).replace("upk::", "")
+    d = re.sub(r"\(.*", "", d.replace("(anonymous namespace)::", "")).replace("upk::", "")
     if flt in d:
         print(f"{d:48s} vgpr {r.get('vgpr', 0):4d} scratch {r.get('scratch', 0):4d} occ {r.get('occ', 0)} "
-              f"vspill {r.get('vspill', 0):3d} sspill {r.get('sspill', 0):3d}")
+              f"lds {r.get('lds', 0):6d} vspill {r.get('vspill', 0):3d} sspill {r.get('sspill', 0):3d}")

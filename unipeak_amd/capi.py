@@ -77,6 +77,8 @@ EXPORTS = [
     "up_last_scan_kind", "up_set_head_place", "up_last_head_kind",
     "up_tir_open", "up_tir_close", "up_tir_set_stream", "up_tir_query", "up_tir_timings",
     "up_cm_open", "up_cm_close", "up_cm_add", "up_cm_collect", "up_cm_timings",
+    "up_dfl_open", "up_dfl_close", "up_dfl_block", "up_dfl_bound", "up_dfl_stream", "up_dfl_segments",
+    "up_dfl_timings", "up_dfl_code_lengths",
 ]
 # (up_set_wide_q11_nd, up_format_g6 and up_g6_to_float are bound in load_library like the rest; they are not listed here because
 # tests/test_capi.py compares this list with the header's names as its pattern reads them,
@@ -167,6 +169,14 @@ def load_library(path=LIB_PATH):
         "up_cm_add": (c.c_int, [vp, c.c_uint64, vp, vp, vp, vp]),
         "up_cm_collect": (c.c_int, [vp, c.c_int, c.POINTER(c.c_uint64), vp, vp, vp, vp, c.c_uint64]),
         "up_cm_timings": (c.c_int, [vp, vp, c.c_int]),
+        "up_dfl_open": (c.c_int, [c.c_int, c.POINTER(vp)]),
+        "up_dfl_close": (None, [vp]),
+        "up_dfl_block": (c.c_uint32, []),
+        "up_dfl_bound": (c.c_uint64, [c.c_uint64]),
+        "up_dfl_stream": (c.c_int, [vp, vp, c.c_uint64, c.POINTER(vp), c.POINTER(c.c_uint64), u32p]),
+        "up_dfl_segments": (c.c_int, [vp, vp, vp, c.c_uint32, c.POINTER(vp), vp]),
+        "up_dfl_timings": (c.c_int, [vp, vp, c.c_int]),
+        "up_dfl_code_lengths": (c.c_int, [vp, c.c_uint32, c.c_uint32, vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("UNIPEAK_LIB") and not hasattr(L, name):
@@ -655,3 +665,68 @@ class CountMap:
             _ck(self.L.up_cm_collect(self.h, int(nondir), ctypes.byref(n), *(o.ctypes.data for o in out),
                                      n.value))
         return tuple(out)
+
+
+def dfl_block():
+    """input bytes per independent block of the device's DEFLATE encoder (up_dfl_block)"""
+    return int(load_library().up_dfl_block())
+
+
+def dfl_bound(n):
+    """upper bound of Deflate.stream's output for n input bytes (up_dfl_bound)"""
+    return int(load_library().up_dfl_bound(int(n)))
+
+
+def dfl_code_lengths(freq, max_len=15):
+    """length-limited Huffman code lengths as the encoder's kernel builds them, on the
+    host (up_dfl_code_lengths): a uint8 array, 0 for an unused symbol"""
+    L = load_library()
+    f = np.ascontiguousarray(freq, np.uint32)
+    out = np.zeros(len(f), np.uint8)
+    _ck(L.up_dfl_code_lengths(f.ctypes.data, len(f), int(max_len), out.ctypes.data))
+    return out
+
+
+class Deflate:
+    """One up_dfl handle: the DEFLATE encoder on the device."""
+
+    def __init__(self, device=0):
+        self.L = load_library()
+        self.h = ctypes.c_void_p()
+        _ck(self.L.up_dfl_open(device, ctypes.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.L.up_dfl_close(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def stream(self, data):
+        """(raw DEFLATE bytes without a final block, CRC-32 of data)"""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        out, n, crc = ctypes.c_void_p(), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _ck(self.L.up_dfl_stream(self.h, buf.ctypes.data if len(buf) else None, len(buf), ctypes.byref(out),
+                                 ctypes.byref(n), ctypes.byref(crc)))
+        return ctypes.string_at(out.value, n.value) if n.value else b"", crc.value
+
+    def segments(self, data, offsets):
+        """one zlib stream per segment data[offsets[i]:offsets[i + 1]], as a list of bytes"""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        n_seg = len(off) - 1
+        out, oo = ctypes.c_void_p(), np.zeros(n_seg + 1, np.uint64)
+        _ck(self.L.up_dfl_segments(self.h, buf.ctypes.data if len(buf) else None, off.ctypes.data, n_seg,
+                                   ctypes.byref(out), oo.ctypes.data))
+        raw = ctypes.string_at(out.value, int(oo[n_seg])) if oo[n_seg] else b""
+        return [raw[int(oo[i]):int(oo[i + 1])] for i in range(n_seg)]
+
+    def timings(self):
+        """[device ms of the kernels, input bytes, output bytes, calls] since open"""
+        t = np.zeros(4, np.float64)
+        _ck(self.L.up_dfl_timings(self.h, t.ctypes.data, 4))
+        return t

@@ -5,9 +5,13 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdlib>
 #include <cstring>
 #include <thread>
 #include <utility>
+
+#include "../../include/unipeak_hip.h"
+#include "cli.hpp"
 
 namespace unipeak {
 namespace bbi {
@@ -113,6 +117,35 @@ bool deflate6(const char *raw, size_t n, std::string &out) {
     return true;
 }
 
+DeviceDeflater::~DeviceDeflater() { up_dfl_close((up_dfl *)h_); }
+
+bool DeviceDeflater::wanted() {
+    const char *e = std::getenv("UNIPEAK_BIGWIG_DEFLATE");
+    return e && std::strcmp(e, "device") == 0;
+}
+
+bool DeviceDeflater::segments(const char *raw, const std::vector<uint64_t> &off, std::vector<std::string> &out) {
+    if (off.size() < 2) return true;
+    if (!h_) {
+        up_dfl *h = nullptr;
+        if (up_dfl_open(cli_physical_device(0), &h) != UP_OK) return false;
+        h_ = h;
+    }
+    const uint32_t n = (uint32_t)(off.size() - 1);
+    std::vector<uint64_t> oo(off.size());
+    const void *p = nullptr;
+    if (up_dfl_segments((up_dfl *)h_, raw, off.data(), n, &p, oo.data()) != UP_OK) return false;
+    out.resize(n);
+    for (uint32_t i = 0; i < n; ++i) out[i].assign((const char *)p + oo[i], (size_t)(oo[i + 1] - oo[i]));
+    return true;
+}
+
+double DeviceDeflater::device_ms() const {
+    double v[1] = {0};
+    if (h_) up_dfl_timings((up_dfl *)h_, v, 1);
+    return v[0];
+}
+
 size_t chrom_tree_bytes(size_t n, size_t key_size) { return 32 + 4 + n * (key_size + 8); }
 
 void write_chrom_tree(std::string &f, const std::vector<std::string> &names, const std::vector<uint32_t> &sizes) {
@@ -149,7 +182,7 @@ void put_section_header(std::string &raw, uint32_t chrom, uint32_t start, uint32
 }
 
 bool write_zoom_level(std::string &f, const ZoomRecord *sm, size_t n, uint32_t reduction, uint32_t &max_raw,
-                      ZoomPlace &place, uint64_t base, unsigned threads) {
+                      ZoomPlace &place, uint64_t base, unsigned threads, DeviceDeflater *dev) {
     place.reduction = reduction;
     place.data = base + f.size();
     put32(f, (uint32_t)n);
@@ -173,7 +206,12 @@ bool write_zoom_level(std::string &f, const ZoomRecord *sm, size_t n, uint32_t r
                 failed = true;
     };
     const unsigned nt = (unsigned)std::min<size_t>(std::max(1u, threads), cut.size());
-    if (nt <= 1) {
+    if (dev) {  // the records are contiguous: the blocks are segments of them
+        std::vector<uint64_t> off;
+        for (const auto &c : cut) off.push_back(c.first * sizeof(ZoomRecord));
+        off.push_back(n * sizeof(ZoomRecord));
+        if (!dev->segments((const char *)sm, off, comp)) failed = true;
+    } else if (nt <= 1) {
         work();
     } else {
         std::vector<std::thread> pool;

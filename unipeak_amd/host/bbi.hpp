@@ -44,6 +44,25 @@ static_assert(sizeof(ZoomRecord) == 32, "bbiSummaryOnDisk");
 // zlib (compress2, level 6) of raw; false when zlib fails
 bool deflate6(const char *raw, size_t n, std::string &out);
 
+// The device's DEFLATE encoder (up_dfl_segments) in deflate6's place: many
+// sections in one call, each an independent zlib stream.  Opt-in
+// (UNIPEAK_BIGWIG_DEFLATE=device); the handle is opened
+// at the first call.
+class DeviceDeflater {
+public:
+    DeviceDeflater() = default;
+    DeviceDeflater(const DeviceDeflater &) = delete;
+    DeviceDeflater &operator=(const DeviceDeflater &) = delete;
+    ~DeviceDeflater();
+    static bool wanted();  // the environment asks for it
+    // raw[off[i], off[i + 1]) -> out[i], each at most 65,536 bytes; false on failure
+    bool segments(const char *raw, const std::vector<uint64_t> &off, std::vector<std::string> &out);
+    double device_ms() const;
+
+private:
+    void *h_ = nullptr;  // up_dfl
+};
+
 // the chromosome B+ tree in one leaf: names in key order, ids 0 .. n - 1
 // (at most 65,535 names: the caller checks)
 void write_chrom_tree(std::string &f, const std::vector<std::string> &names, const std::vector<uint32_t> &sizes);
@@ -54,13 +73,14 @@ size_t chrom_tree_bytes(size_t n, size_t key_size);
 void put_section_header(std::string &raw, uint32_t chrom, uint32_t start, uint32_t end, uint32_t span, uint16_t n);
 
 // a zoom level at file offset base + f.size(), its blocks compressed on
-// `threads` threads (the bytes do not depend on it): false when zlib fails
+// `threads` threads (the bytes do not depend on it), or by dev in one call
+// when it is given: false when the compression fails
 struct ZoomPlace {
     uint32_t reduction;
     uint64_t data, index;
 };
 bool write_zoom_level(std::string &f, const ZoomRecord *rec, size_t n, uint32_t reduction, uint32_t &max_raw,
-                      ZoomPlace &place, uint64_t base = 0, unsigned threads = 1);
+                      ZoomPlace &place, uint64_t base = 0, unsigned threads = 1, DeviceDeflater *dev = nullptr);
 
 // header + zoom headers (kHeaderBytes + kZoomHeaderBytes per level)
 std::string header_bytes(uint64_t tree_off, uint64_t data_off, uint64_t index_off, uint64_t summary_off,

@@ -913,6 +913,7 @@ struct BwTrack {
         put(std::string(data_off + 8, '\0'));  // + the section count
     }
     // the sections of n items of one chunk (sec: their records, or null), compressed on T threads
+    bbi::DeviceDeflater *dev = nullptr;  // UNIPEAK_BIGWIG_DEFLATE=device: sections and zoom blocks go through it
     void add_sections(uint32_t chrom, const up_bw_item *it, size_t n, const up_bw_section *sec, unsigned T,
                       BigWigStats &st) {
         if (!n) return;
@@ -921,6 +922,21 @@ struct BwTrack {
         std::vector<up_bw_section> rec(nsec);
         std::atomic<size_t> next{0};
         std::atomic<bool> failed{false};
+        // the device's encoder: every section's header and items in one buffer, one call
+        auto on_device = [&] {
+            std::string raw;
+            raw.reserve(n * sizeof(up_bw_item) + nsec * bbi::kSectionHeaderBytes);
+            std::vector<uint64_t> off(nsec + 1, 0);
+            for (size_t s = 0; s < nsec; ++s) {
+                const up_bw_item *a = it + s * bbi::kItemsPerSection;
+                const size_t k = std::min<size_t>(bbi::kItemsPerSection, n - s * bbi::kItemsPerSection);
+                rec[s] = sec ? sec[s] : bw_host_section(a, k);
+                bbi::put_section_header(raw, chrom, rec[s].start, rec[s].end, 1, (uint16_t)k);
+                raw.append((const char *)a, k * sizeof(up_bw_item));
+                off[s + 1] = raw.size();
+            }
+            if (!dev->segments(raw.data(), off, comp)) failed = true;
+        };
         auto work = [&] {
             std::string raw;
             for (size_t s; (s = next.fetch_add(1)) < nsec;) {
@@ -935,7 +951,9 @@ struct BwTrack {
         };
         const auto t0 = std::chrono::steady_clock::now();
         const unsigned nt = (unsigned)std::min<size_t>(T, nsec);
-        if (nt <= 1) {
+        if (dev) {
+            on_device();
+        } else if (nt <= 1) {
             work();
         } else {
             std::vector<std::thread> pool;
@@ -980,7 +998,7 @@ struct BwTrack {
             f.clear();
             bbi::ZoomPlace place{};
             if (!bbi::write_zoom_level(f, (const bbi::ZoomRecord *)zoom[z].data(), zoom[z].size(), (uint32_t)red,
-                                       max_raw, place, at, T))
+                                       max_raw, place, at, T, dev))
                 fatal("-W: compression failed");
             put(f);
             places.push_back(place);
@@ -1046,8 +1064,11 @@ void write_profile_bigwig(const PassResult &pr, uint16_t bw, BigWigSink &sink) {
             return ct.name(pr.units[x].contig) < ct.name(pr.units[y].contig);
         });
     }
+    bbi::DeviceDeflater deflater;
+    const bool on_device = bbi::DeviceDeflater::wanted();
     for (int b = 0; b < ntracks; ++b) {
         BwTrack t;
+        if (on_device) t.dev = &deflater;
         t.path = sink.root + (sink.directional ? (b ? "-" : "+") : "") + ".bw";
         t.red0 = red0;
         if (units[b].size() > 65535) fatal("-W: too many chromosomes for one B+ tree node");
@@ -1153,6 +1174,8 @@ void write_profile_bigwig(const PassResult &pr, uint16_t bw, BigWigSink &sink) {
         }
         t.finish(T, st);
     }
+    st.deflate_device = on_device;
+    st.deflate_ms = deflater.device_ms();
 }
 
 void release_devices() {

@@ -138,6 +138,8 @@ struct BigWigStats {
     double bigwig_ms = 0, dense_ms = 0;
     double compress_s = 0;  // wall time in the data sections' compression
     double trailer_s = 0;   // R-tree, zoom levels (compressed on the same pool), header
+    bool deflate_device = false;  // UNIPEAK_BIGWIG_DEFLATE=device: the device's encoder, not the zlib pool
+    double deflate_ms = 0;        // its kernels
 };
 
 struct BigWigSink {

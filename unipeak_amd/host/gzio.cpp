@@ -3,11 +3,16 @@
 // the CLIs keeps its FILE* code path.
 #include "gzio.hpp"
 
+#include <sys/stat.h>
 #include <zlib.h>
 
 #include <cerrno>
+#include <cstdlib>
 #include <cstring>
 
+#include "../../include/unipeak_hip.h"
+#include "cli.hpp"
+#include "gzdev.hpp"
 #include "wigio.hpp"
 
 namespace unipeak {
@@ -35,7 +40,14 @@ namespace {
 struct GzCookie {
     gzFile g;
     std::string name;
+    uint64_t in = 0;      // bytes written through it
+    bool timing = false;  // UNIPEAK_TIMING: a "gz" line at close
 };
+
+bool env_on(const char *name) {
+    const char *e = std::getenv(name);
+    return e && *e && *e != '0';
+}
 
 ssize_t gz_read(void *c, char *buf, size_t n) {
     GzCookie *k = (GzCookie *)c;
@@ -52,14 +64,67 @@ ssize_t gz_write(void *c, const char *buf, size_t n) {
         if (w <= 0) return done ? (ssize_t)done : -1;
         done += (size_t)w;
     }
+    k->in += done;
     return (ssize_t)done;
 }
 
 int gz_close(void *c) {
     GzCookie *k = (GzCookie *)c;
     const int r = gzclose(k->g);
+    if (k->timing && r == Z_OK) {
+        struct stat sb;
+        const unsigned long long out = stat(k->name.c_str(), &sb) == 0 ? (unsigned long long)sb.st_size : 0;
+        std::fprintf(stderr, "[timing] gz %s in %llu B out %llu B members 1 device 0.000 ms path zlib\n",
+                     k->name.c_str(), (unsigned long long)k->in, out);
+    }
     delete k;
     return r == Z_OK ? 0 : EOF;
+}
+
+// the device's DEFLATE encoder (up_dfl_stream) as the batch writer's compressor
+class DeviceCompressor : public GzCompressor {
+public:
+    explicit DeviceCompressor(up_dfl *h) : h_(h) {}
+    ~DeviceCompressor() override { up_dfl_close(h_); }
+    bool stream(const void *src, uint64_t n, const void **out, uint64_t *n_out, uint32_t *crc32) override {
+        rc_ = up_dfl_stream(h_, src, n, out, n_out, crc32);
+        return rc_ == UP_OK;
+    }
+    double device_ms() const override {
+        double v[1] = {0};
+        up_dfl_timings(h_, v, 1);
+        return v[0];
+    }
+    std::string error() const override { return up_strerror(rc_); }
+
+private:
+    up_dfl *h_;
+    int rc_ = UP_OK;
+};
+
+std::unique_ptr<GzCompressor> make_device_compressor(std::string *err) {
+    up_dfl *h = nullptr;
+    const int rc = up_dfl_open(cli_physical_device(0), &h);
+    if (rc != UP_OK) {
+        *err = up_strerror(rc);
+        return nullptr;
+    }
+    return std::unique_ptr<GzCompressor>(new DeviceCompressor(h));
+}
+
+ssize_t gzb_write(void *c, const char *buf, size_t n) {
+    GzBatchWriter *w = (GzBatchWriter *)c;
+    if (!w->write(buf, n)) fatal("could not write gzip output: " + w->error());
+    return (ssize_t)n;
+}
+
+int gzb_close(void *c) {
+    GzBatchWriter *w = (GzBatchWriter *)c;
+    const bool ok = w->close();
+    const std::string err = w->error();
+    delete w;
+    if (!ok) fatal("could not write gzip output: " + err);
+    return 0;
 }
 // the reference's gzip filter (boost gzip_decompressor, misc/filterstream.cpp:
 // 30-50) throws on a file without a gzip header; zlib would read it as plain
@@ -108,11 +173,23 @@ FILE *open_input(const std::string &fname) {
 FILE *open_output(const std::string &fname) {
     if (is_bz2(fname)) no_bz2(fname, "write");
     if (!is_gz(fname)) return std::fopen(fname.c_str(), "wb");
+    const bool timing = env_on("UNIPEAK_TIMING");
+    const char *dev = std::getenv("UNIPEAK_GZ_DEVICE");
+    if (!dev || std::atoi(dev) != 0) {  // batches through the device's encoder (gzdev.hpp)
+        size_t batch = kGzBatchDefault;
+        if (const char *e = std::getenv("UNIPEAK_GZ_BATCH")) batch = (size_t)std::strtoull(e, nullptr, 10);
+        batch = std::max<size_t>(batch, up_dfl_block());
+        GzBatchWriter *w = new GzBatchWriter(fname, batch, make_device_compressor, timing);
+        cookie_io_functions_t io{nullptr, gzb_write, nullptr, gzb_close};
+        FILE *f = w->open() ? fopencookie(w, "w", io) : nullptr;
+        if (!f) delete w;
+        return f;
+    }
     gzFile g = gzopen(fname.c_str(), "wb");
     if (!g) return nullptr;
     gzbuffer(g, 1u << 20);
     cookie_io_functions_t io{nullptr, gz_write, nullptr, gz_close};
-    GzCookie *k = new GzCookie{g, fname};
+    GzCookie *k = new GzCookie{g, fname, 0, timing};
     FILE *f = fopencookie(k, "w", io);
     if (!f) {
         gzclose(g);

@@ -248,11 +248,13 @@ int main(int argc, char **argv) {
         if (const char *e = std::getenv("UNIPEAK_TIMING"); e && *e && *e != '0')
             std::fprintf(stderr,
                          "[timing] bigwig: device %llu items, host %llu items, fallback chunks %llu of %llu, "
-                         "sections %llu, kernels bigwig %.3f ms dense %.3f ms, compress %.3f s, trailer %.3f s\n",
+                         "sections %llu, kernels bigwig %.3f ms dense %.3f ms, compress %.3f s, trailer %.3f s, deflate %s "
+                         "%.3f ms\n",
                          (unsigned long long)bws.stats.device_items, (unsigned long long)bws.stats.host_items,
                          (unsigned long long)bws.stats.fallback_chunks, (unsigned long long)bws.stats.chunks,
                          (unsigned long long)bws.stats.sections, bws.stats.bigwig_ms, bws.stats.dense_ms,
-                         bws.stats.compress_s, bws.stats.trailer_s);
+                         bws.stats.compress_s, bws.stats.trailer_s, bws.stats.deflate_device ? "device" : "zlib",
+                         bws.stats.deflate_ms);
     }
 
     // emission in the reference's order (Q2-Q4); Q3 drops final-flush regions
