@@ -230,6 +230,8 @@ int up_reset_units(up_ctx *ctx);
  * slower than the scans); up_run_async and up_unit_profile* refuse those
  * (UP_E_UNSUPPORTED).  up_shift_scan correlates a
  * replayed region's stored scores (Region::scores), as strandCorr does.
+ * UNIPEAK_WIDE, UNIPEAK_Q11_REPLAY and UNIPEAK_Q11_HEADS are read at up_open
+ * like the other switches that pick a scan (csrc/route.h holds the policy).
  * With a threshold <= 0 the last region of a unit is still open after its
  * flush and is closed in the buffer's next unit (UP_CLOSE_Q11_HEAD); the
  * last region of a buffer's last unit in the context is never closed (the

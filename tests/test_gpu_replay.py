@@ -107,8 +107,10 @@ def test_replay_multi_sample_control_and_coeffs(gpu_lib, oracle):
 
 
 def test_replay_refuses_pipelined_and_profile(gpu_lib):
-    """bw > 511 (kMaxBw) on a nondirectional unit: outside the parallel scans
-    (K1 and the directional K1w), the segmented replay"""
+    """bw > 511 (kMaxBw) on a nondirectional unit in a library context that has
+    not set up_set_wide_nd_full: K1w inside a blocking-only pass (csrc/route.h),
+    so up_run_async and the dense profile are refused as they are for the
+    replay"""
     capi = gpu_lib
     with capi.Lib(0) as g:
         g.set_params(600, 1, 0.003, nondir=True)

@@ -14,6 +14,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <thread>
 #include <type_traits>
 #include <vector>
@@ -21,6 +22,7 @@
 #include "../../include/unipeak_hip.h"
 #include "devmem.h"
 #include "kernels.h"
+#include "route.h"
 
 #include "kernels.hip"  // device code shared with the per-NH units (nh_tu.hip)
 #include "stats1.hip"   // (its LDS size)
@@ -107,11 +109,11 @@ struct up_ctx {
     int k1b_blocks = 0;              // K1b grid of exactly this many workgroups (UNIPEAK_K1B_BLOCKS; tests, A/B)
     bool k1b_one = true;             // pipelined K1b for one directional sample (UNIPEAK_K1B_ONE=0: off)
     bool k3_one = true;              // batched K3 for one directional sample (UNIPEAK_K3_ONE=0: off)
-    bool wide_nd = true;             // K1w for nondirectional units (UNIPEAK_WIDE_ND=0: the replay)
-    bool wide_nd_full = false;       // those units' -w capture, dense profile and up_run_async (up_set_wide_nd_full)
-    bool wide_q11 = true;            // wide K1q: threshold <= 0 at bw 512 .. 32,767 (UNIPEAK_WIDE_Q11=0: the replay)
+    // what decides a pass's route beside the parameters (route.h, route_of)
+    Switches sw;                     // the environment switches
+    bool wide_nd_full = false;       // nondirectional K1w: the -w capture, dense profile and up_run_async (up_set_wide_nd_full)
     bool wide_q11_nd = false;        // wide K1q for nondirectional units as well (up_set_wide_q11_nd)
-    bool wide_q11_nd_env = true;     // UNIPEAK_WIDE_Q11_ND=0: the replay for them whatever the switch says
+    bool coef_nonneg = true;         // no -z coefficient is negative or NaN (up_set_params)
     // the strand correlation behind nondirectional wide K1q (wide.hip): regions of
     // more than corr_long stored positions take the stage / chain kernels, whose
     // staging area holds corr_tile positions (test-only overrides, read at up_open:
@@ -264,13 +266,13 @@ struct up_ctx {
         uint64_t req_reg_cap = 0;    // record / overflow capacities: the caller's thread
         uint32_t req_ovf_cap = 0;    // grows them, the launcher thread only reads these
         int req_tl = 0;
-        bool req_q11 = false;
+        Scan req_scan = Scan::K1;    // the route's scan (never the replay: it launches no pass)
         // the pass replays and places its head units itself (up_set_head_place),
         // with these K0 capacities (emu_reg_cap, emu_out_cap, emu_scores_cap)
         bool req_head_place = false, head_place = false;
         uint32_t req_emu_reg_cap = 0, req_emu_out_cap = 0, k0_out_cap = 0;
         uint64_t req_emu_scores_cap = 0;
-        bool req_q11_place = false;  // the pass places its K1q records (q11_place)        // K1q instead of K1a/K1x/K1b (threshold <= 0, run_q11)
+        bool req_q11_place = false;  // the pass places its K1q records (q11_place)
         bool lpending = false;       // queued for / being launched by the launcher thread
         int lrc = 0;                 // its launch result
         uint64_t cap = 0;            // reg_cap at launch
@@ -278,7 +280,6 @@ struct up_ctx {
         int tl = 0;                  // timing level at launch
         int k1b_kind = -1;           // the K1b this pass launches (up_last_exact_kind)
         int k3_kind = -1;            // the K3 dispatch_stats picks for this pass (up_last_stats_kind)
-        int scan_kind = -1;          // the scan this pass launches: 0 K1, 1 K1w, 2 K1q (up_last_scan_kind)
         std::chrono::steady_clock::time_point t0;
         Event ev[5];                 // K1a begin, K1a end, K1b end, K2 end, K3 end
         Event hev[3];                // a placed pass at timing level 2: K0 begin, K0 end, placement end
@@ -350,11 +351,9 @@ struct up_ctx {
     Event k0_done;
     bool k0_done_set = false;
     HostBuf<uint32_t> hp_resync[kSlots];
-    // threshold <= 0 through K1q (run_q11): the blocking pass in progress,
-    // and per host record the unit whose tracks hold its positions (a region
-    // closed in the buffer's next unit keeps the previous unit's positions)
-    bool q11_run = false;
-    bool wide_nd_run = false;  // the blocking pass of a nondirectional K1w context in progress (run_wide_nd)
+    // threshold <= 0 through K1q (run_q11): per host record the unit whose
+    // tracks hold its positions (a region closed in the buffer's next unit
+    // keeps the previous unit's positions)
     DevBuf<uint32_t> d_q11_head;
     // K1q records finished on the device (q11place.hip): K3's stage, the
     // per-unit placement, the head chains' edits, and per placed record its
@@ -395,10 +394,17 @@ struct up_ctx {
     uint64_t last_nreg = 0;
     int last_k1b_kind = -1;  // K1b of the pass completed last (up_last_exact_kind)
     int last_k3_kind = -1;  // K3 of the pass completed last (up_last_stats_kind)
-    int last_scan_kind = -1;  // how the pass completed last found its regions (up_last_scan_kind)
+    std::optional<Scan> last_scan;  // how the pass completed last found its regions (up_last_scan_kind)
 };
 
 static bool busy(const up_ctx *c) { return c && c->seq_launched != c->seq_done; }
+
+// the route of the context's next pass: a handful of compares, per call
+static Route route_of(const up_ctx *c) {
+    return route_for({c->p.bw, c->p.region_thr > 0, c->coef_nonneg, c->p.nondir != 0, c->prof_capture,
+                      c->wide_nd_full, c->wide_q11_nd, kTB, c->sw},
+                     kMaxBw, kMaxWideBw);
+}
 
 // the tracks or the pooling changed: the index is rebuilt when a pass wants it
 // (the per-unit dirty flags say what), and UP_INDEX_AUTO counts passes anew
@@ -433,8 +439,6 @@ int up_track_bits(void) { return kTB; }
 static bool plane_scan(const up_ctx *c);
 static int pool_mode(const up_ctx *c);
 static bool pct_mode(const up_ctx *c);
-static bool wide_mode(const up_ctx *c);
-static bool wide_q11_mode(const up_ctx *c);
 
 static bool want_index(const up_ctx *c);
 
@@ -471,7 +475,7 @@ int up_index_state(up_ctx *c, int *on, uint64_t *builds) {
 
 int up_last_stats_kind(up_ctx *c) { return c ? c->last_k3_kind : -1; }
 int up_last_exact_kind(up_ctx *c) { return c ? c->last_k1b_kind : -1; }
-int up_last_scan_kind(up_ctx *c) { return c ? c->last_scan_kind : -1; }
+int up_last_scan_kind(up_ctx *c) { return c && c->last_scan ? scan_kind(*c->last_scan) : -1; }
 int up_last_head_kind(up_ctx *c) { return c ? c->last_head_kind : -1; }
 
 const char *up_strerror(int code) {
@@ -532,6 +536,17 @@ int up_g6_to_float(double v, float *out, int *ok) {
     return UP_OK;
 }
 
+static Switches read_switches() {
+    Switches sw;
+    if (const char *e = getenv("UNIPEAK_WIDE")) sw.wide = *e != '0';
+    if (const char *e = getenv("UNIPEAK_WIDE_ND")) sw.wide_nd = atoi(e) != 0;
+    if (const char *e = getenv("UNIPEAK_WIDE_Q11")) sw.wide_q11 = atoi(e) != 0;
+    if (const char *e = getenv("UNIPEAK_WIDE_Q11_ND")) sw.wide_q11_nd = atoi(e) != 0;
+    if (const char *e = getenv("UNIPEAK_Q11_REPLAY")) sw.q11_replay = *e && *e != '0';
+    if (const char *e = getenv("UNIPEAK_Q11_HEADS")) sw.q11_heads_replay = std::strcmp(e, "replay") == 0;
+    return sw;
+}
+
 int up_open(int hip_device, up_ctx **out) {
     if (!out) return UP_E_ARG;
     int n = 0;
@@ -548,9 +563,7 @@ int up_open(int hip_device, up_ctx **out) {
     if (const char *e = getenv("UNIPEAK_K3_PER_CU")) c->k3_per_cu = atoi(e);
     if (const char *e = getenv("UNIPEAK_K3_ONE")) c->k3_one = atoi(e) != 0;
     if (const char *e = getenv("UNIPEAK_K1B_ONE")) c->k1b_one = atoi(e) != 0;
-    if (const char *e = getenv("UNIPEAK_WIDE_ND")) c->wide_nd = atoi(e) != 0;
-    if (const char *e = getenv("UNIPEAK_WIDE_Q11")) c->wide_q11 = atoi(e) != 0;
-    if (const char *e = getenv("UNIPEAK_WIDE_Q11_ND")) c->wide_q11_nd_env = atoi(e) != 0;
+    c->sw = read_switches();
     if (const char *e = getenv("UNIPEAK_WIDE_CORR_LONG")) c->corr_long = std::max<uint64_t>(4, strtoull(e, nullptr, 10));
     if (const char *e = getenv("UNIPEAK_WIDE_CORR_TILE")) c->corr_tile = std::max<uint64_t>(64, strtoull(e, nullptr, 10));
     if (const char *e = getenv("UNIPEAK_PROFILE_TEXT_LIMIT")) c->text_limit = strtod(e, nullptr);
@@ -642,6 +655,7 @@ int up_set_params(up_ctx *c, const up_params *p) {
     c->p = *p;
     c->p.is_control = nullptr;
     c->p.coeffs = nullptr;
+    c->coef_nonneg = std::all_of(coef.begin(), coef.end(), [](double q) { return q >= 0; });
     if (!same) {
         c->head_tab_valid = false;  // (the head flags follow the pooling)
         c->ctl = ctl;
@@ -754,7 +768,8 @@ static void set_q_params(up_ctx *c) {
 // 2^32 for the largest possible window, and distinct Q ordering the FP64
 // scores: alpha (Q+1)(1 - delta) > alpha Q (1 + delta) for every Q <= Qmax
 static bool q_mode(const up_ctx *c) {
-    if (!c->q_ok || !c->coef.empty() || c->nc.empty() || c->p.bw > kMaxBw) return false;
+    // (q_ok: a threshold > 0 at a narrow bandwidth, i.e. Scan::K1 -- set_q_params)
+    if (!c->q_ok || !c->coef.empty() || c->nc.empty()) return false;
     // several pooled samples: K3 would score each peak from every sample's
     // window bytes, which cost more than the keys save in K1b (hg19, 8
     // samples + 1 control: K1b 2.07 -> 1.64 ms but K3 0.82 -> 1.08-1.23 ms,
@@ -1258,7 +1273,7 @@ static int sync_layout(up_ctx *c) {
 // from the packed tracks.  K1w screens on the planes, so it always does.
 static bool want_index(const up_ctx *c) {
     if (kTB != 2) return false;
-    if (wide_mode(c) || wide_q11_mode(c)) return true;  // (wide K1q's peaks screen on them as well)
+    if (is_wide(route_of(c).scan)) return true;  // (wide K1q's peaks screen on them as well)
     switch (c->index_policy) {
     case UP_INDEX_ALWAYS: return true;
     case UP_INDEX_NEVER: return false;
@@ -1494,7 +1509,7 @@ static void dispatch_scan(up_ctx *c, hipStream_t st, const ScanParams &P, uint32
 // the Q keys on: exact1.hip; UNIPEAK_K1B_ONE=0 keeps the generic kernel, for
 // A/B and tests), 0 scan_kernel's exact mode
 static int k1b_kind_for(const up_ctx *c) {
-    return c->k1b_one && kTB == 2 && pool_mode(c) == 0 && c->p.nondir == 0 && c->p.bw <= kMaxBw && q_mode(c) ? 1 : 0;
+    return c->k1b_one && kTB == 2 && pool_mode(c) == 0 && c->p.nondir == 0 && q_mode(c) ? 1 : 0;
 }
 
 static void dispatch_exact(up_ctx *c, hipStream_t st, const ScanParams &P, uint32_t ns) {
@@ -1618,96 +1633,6 @@ static void dispatch_stats(up_ctx *c, hipStream_t st, const StatParams &P, uint6
     (void)hipLaunchKernel(k, dim3((unsigned)blocks), dim3(kind == 2 ? kK3LThreads : 256), args, lds, st);
 }
 
-// Configurations the parallel scan does not represent run through the
-// exact state machine over every unit (K0 replay, emulate.hip): a threshold
-// <= 0 makes the leap branch of processPosition live (quirk Q11, the leap
-// position joins a region without setting its left end), and kernels wider
-// than kMaxBw exceed the scan's register-resident halo.
-// A threshold <= 0 with non-negative scores (no negative coefficient) runs
-// in parallel instead (K1q, run_q11): every processed position qualifies, so
-// regions are the runs of processed positions; units that start processing
-// at position 1 still take the replay.  UNIPEAK_Q11_REPLAY=1: always replay.
-// Up to kMaxBw K1q's own run kernel (proc_runs_kernel) and K3's KDE; wider,
-// up to kMaxWideBw, wide K1q (wide_q11_mode below).
-static bool q11_scores_ok(const up_ctx *c) {
-    if (c->p.region_thr > 0 || kTB != 2) return false;
-    for (double q : c->coef)
-        if (!(q >= 0)) return false;
-    static const bool off = [] {
-        const char *e = getenv("UNIPEAK_Q11_REPLAY");
-        return e && *e && *e != '0';
-    }();
-    return !off;
-}
-
-static bool q11_mode(const up_ctx *c) { return q11_scores_ok(c) && (c->p.bw <= kMaxBw || wide_q11_mode(c)); }
-
-// UNIPEAK_Q11_HEADS=replay: units that process position 1 send the whole
-// context to the whole-buffer replay (round 4's rule; A/B and tests)
-static bool q11_whole_replay() {
-    static const bool on = [] {
-        const char *e = getenv("UNIPEAK_Q11_HEADS");
-        return e && std::strcmp(e, "replay") == 0;
-    }();
-    return on;
-}
-
-// K1w (wide.hip) for kernels wider than K1's halo: a threshold > 0 (directional
-// units with the -w capture on as well: head units hand their
-// retirements over from the K0 head replay, wide_profile_kernel gives the
-// dense rest; nondirectional units by default only with the capture off, and
-// only inside the blocking up_run -- wide_nd_mode; up_set_wide_nd_full lifts
-// both), and a window of at most 65,535 cells
-// (bw <= kMaxWideBw): the reference counts
-// the cells add() retires in a UShort (misc/peakcall.cpp:172-177), so from
-// bw 32,768 on a gap of 2bw + 1 or more retires (gap mod 65,536) cells, the
-// rest of the window stays misaligned and a flush leaks into the buffer's
-// next unit -- only the whole-buffer replay models that (emulate.hip);
-// UNIPEAK_WIDE=0: the replay instead; UNIPEAK_WIDE_ND=0 (read at up_open):
-// the replay for nondirectional units only
-static bool wide_on() {
-    static const bool on = [] {
-        const char *e = getenv("UNIPEAK_WIDE");
-        return !(e && *e == '0');
-    }();
-    return on;
-}
-
-static bool wide_mode(const up_ctx *c) {
-    const bool on = wide_on();
-    return on && c->p.bw > kMaxBw && c->p.bw <= kMaxWideBw && kTB == 2 && c->p.region_thr > 0 &&
-           (!c->p.nondir || (c->wide_nd && (!c->prof_capture || c->wide_nd_full)));
-}
-
-// K1w over both strands: by default its passes run only inside the blocking
-// up_run (run_wide_nd, as K1q's inside run_q11) and up_run_async and the
-// dense profile of these units stay refused; with up_set_wide_nd_full on,
-// nothing is (the pass state is per slot: d_wcorr and d_wslab, the
-// correlation kernel on the pass stream, no captured graph behind K1w)
-static bool wide_nd_mode(const up_ctx *c) { return c->p.nondir && wide_mode(c); }
-
-// wide K1q (wide.hip): a threshold <= 0 with non-negative scores at kMaxBw <
-// bw <= kMaxWideBw, the -w capture off: wide_runs_kernel finds the runs of
-// processed positions (over every strand's tracks), wide_peak_kernel their
-// peaks, K2 / K3 / the placement and the K0 head chains follow as behind
-// narrow K1q (run_q11), so its passes too run only inside the blocking up_run.
-// Nondirectional units take it only with up_set_wide_q11_nd on (off by
-// default: the replay): their peaks are those of forwardScore + reverseScore
-// (wide_peak_kernel<POOL, true>), and one region can span a contig, so the
-// strand correlation of a region of more than corr_long stored positions is
-// staged by many waves and chained by one (launch_wide_corr_long).
-// UNIPEAK_WIDE_Q11=0 (read at up_open): the replay (A/B, tests);
-// UNIPEAK_WIDE_Q11_ND=0 (read at up_open): the replay for nondirectional
-// units whatever the switch says.
-static bool wide_q11_mode(const up_ctx *c) {
-    return c->wide_q11 && wide_on() && q11_scores_ok(c) && c->p.bw > kMaxBw && c->p.bw <= kMaxWideBw &&
-           (!c->p.nondir || (c->wide_q11_nd && c->wide_q11_nd_env)) && !c->prof_capture;
-}
-
-static bool replay_mode(const up_ctx *c) {
-    return (c->p.bw > kMaxBw && !wide_mode(c) && !wide_q11_mode(c)) || (!(c->p.region_thr > 0) && !q11_mode(c));
-}
-
 static int check_params(up_ctx *c) {
     if (!c || !c->have_params) return UP_E_STATE;
     if (c->p.bw < 1) return UP_E_ARG;
@@ -1715,16 +1640,13 @@ static int check_params(up_ctx *c) {
     return UP_OK;
 }
 
-// the parallel scan; K1q passes only inside the blocking up_run (their
-// records are finished on the host), K1q's dense profile always
-static int check_runnable(up_ctx *c, bool profile = false) {
-    int r = check_params(c);
-    if (r) return r;
-    if (replay_mode(c)) return UP_E_UNSUPPORTED;
-    // (the dense profile's window is K1's, or wide_profile_kernel's where K1w runs)
-    if (profile && c->p.bw > kMaxBw && !wide_mode(c) && !wide_q11_mode(c)) return UP_E_UNSUPPORTED;
-    if (wide_nd_mode(c) && !c->wide_nd_full && (profile || !c->wide_nd_run)) return UP_E_UNSUPPORTED;
-    return q11_mode(c) && !c->q11_run && !profile ? UP_E_UNSUPPORTED : UP_OK;
+// what a caller may ask of the context's route: a pass through up_run_async,
+// or the dense profile (*scan: the route's scan)
+static int check_runnable(up_ctx *c, bool profile, Scan *scan = nullptr) {
+    if (int r = check_params(c)) return r;
+    const Route rt = route_of(c);
+    if (scan) *scan = rt.scan;
+    return (profile ? rt.profile_ok : rt.async_ok) ? UP_OK : UP_E_UNSUPPORTED;
 }
 
 // Quirk Q1: units whose pooled hits include a position <= bw are replayed
@@ -2186,7 +2108,7 @@ static int q11_place(up_ctx *c, int slot, hipStream_t st, const Q11Edit *d_edit,
 // (headplace.hip): the mode is on, a threshold > 0, the -w capture off (its
 // entries are gathered on the host, emulate_units)
 static bool head_place_mode(const up_ctx *c) {
-    return c->head_place && c->p.region_thr > 0 && !c->prof_capture && !c->q11_run;
+    return c->head_place && c->p.region_thr > 0 && !c->prof_capture;
 }
 
 // the layout-time tables of head_place_mode: head flags, "aligned" flags and
@@ -2443,7 +2365,7 @@ static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatPar
     up_ctx::Pass &ps = c->pass[slot];
     const uint32_t ns = c->nstrips;
     const uint32_t nsb = (ns + kSegBlock - 1) / kSegBlock;
-    if (!ps.req_q11 && c->p.bw <= kMaxBw) {  // (K1q and K1w wrote every strip's runs themselves)
+    if (ps.req_scan == Scan::K1) {  // (K1q and K1w wrote every strip's runs themselves)
         if (k1a_waves) {  // K1x: list the stashed work-list entries for K1b
             hipLaunchKernelGGL(xref_kernel, dim3(1), dim3(1024), 0, ps.stream, ps.d_xwcount.p, k1a_waves,
                                k1a_xcap, ps.d_xref.p, ps.d_xcount.p);
@@ -2463,8 +2385,8 @@ static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatPar
                        c->hp_status[slot].dev, thdr);
     HIPCHK(hipGetLastError());
     if (events) HIPCHK(hipEventRecord(ps.ev[3], ps.stream));
-    if (ps.req_q11 && c->p.bw > kMaxBw) {  // wide K1q: every region's peak (wide.hip) into the arrays K3
-                                           // reads as known peaks (timed with K3: up_timings [2])
+    if (ps.req_scan == Scan::K1qWide) {  // every region's peak (wide.hip) into the arrays K3
+                                         // reads as known peaks (timed with K3: up_timings [2])
         const uint32_t lcap = wide_list_cap();
         const size_t lds = prof_lds_bytes(c->p.bw);
         const bool nd = c->p.nondir != 0;  // (up_set_wide_q11_nd: peaks of forwardScore + reverseScore)
@@ -2493,14 +2415,14 @@ static int enqueue_rest(up_ctx *c, int slot, const ScanParams &SP, const StatPar
         const size_t lds = corr_lds_bytes(c->p.bw);
         const uint32_t lcap = wide_list_cap();
         // (behind wide K1q a region can span a contig: the long ones go to launch_wide_corr_long)
-        const uint64_t long_n = ps.req_q11 ? c->corr_long : ~0ull;
+        const uint64_t long_n = ps.req_scan == Scan::K1qWide ? c->corr_long : ~0ull;
         with_pool_mode(pool_mode(c), [&](auto pm) {
             hipLaunchKernelGGL(wide_corr_kernel<decltype(pm)::value>, dim3(blocks), dim3(64), lds, ps.stream, SP,
                                ps.d_starts.p, ps.d_ends.p, ps.d_runit.p, ps.d_nreg.p, (uint64_t)cap, ps.d_wslab.p,
                                lcap, ps.d_wcorr.p, long_n);
         });
         HIPCHK(hipGetLastError());
-        if (ps.req_q11)
+        if (ps.req_scan == Scan::K1qWide)
             if (int r = launch_wide_corr_long(c, ps, SP, cap)) return r;
     }
     dispatch_stats(c, ps.stream, P, std::max<uint64_t>(ps.req_last_nreg, 1024));
@@ -2543,6 +2465,7 @@ static int launch_pass(up_ctx *c, int slot) {
     // every per-pass decision reads the request snapshot (ps.req_*), never
     // the live context: the caller may change the record target or grow the
     // capacities while this pass waits for the launcher thread
+    const Scan scan = ps.req_scan;
     const uint64_t cap = ps.req_reg_cap;
     const uint32_t ovf_cap = ps.req_ovf_cap;
     HIPCHK(ps.d_ovf_rec.ensure((size_t)ovf_cap * kOvfStride));
@@ -2557,13 +2480,13 @@ static int launch_pass(up_ctx *c, int slot) {
     // at most 8 resident 4-wave workgroups per CU
     const bool corr = c->p.nondir && (c->p.want_corr || c->p.corr_thr > -1);
     const uint32_t corr_cap = 1024;
-    const bool wcorr = corr && c->p.bw > kMaxBw;  // K1w: wide_corr_kernel instead of K3's KDE
+    const bool wcorr = corr && is_wide(scan);  // wide_corr_kernel instead of K3's KDE
     if (corr && !wcorr) HIPCHK(ps.d_corr.ensure((size_t)(c->ncu > 0 ? c->ncu : 256) * 8 * 4 * corr_cap * 2));
     if (wcorr) {
         HIPCHK(ps.d_wcorr.ensure(cap + 1));
         HIPCHK(ps.d_wslab.ensure((size_t)wide_corr_blocks(c) * 2 * kCorrSlab));
     }
-    if (wcorr && ps.req_q11) {  // the long regions' stage and chain kernels
+    if (wcorr && scan == Scan::K1qWide) {  // the long regions' stage and chain kernels
         // (the regions of a unit are disjoint: the strips' positions bound the axis)
         c->wc_stage_cap = std::min<uint64_t>(c->corr_tile, (uint64_t)ns * kStrip);
         HIPCHK(c->d_wc_ioff.ensure(cap + 2));
@@ -2571,9 +2494,8 @@ static int launch_pass(up_ctx *c, int slot) {
         HIPCHK(c->d_wc_carry.ensure(5 * (cap + 1)));
         HIPCHK(c->d_wc_stage.ensure(2 * c->wc_stage_cap + 2));
     }
-    if (ps.req_q11 && c->p.bw > kMaxBw && c->p.nondir)
-        HIPCHK(c->d_wq_fstash.ensure((size_t)wide_peak_nd_blocks(c) * kCorrSlab));
-    if (ps.req_q11 && c->p.bw > kMaxBw) {
+    if (scan == Scan::K1qWide) {
+        if (c->p.nondir) HIPCHK(c->d_wq_fstash.ensure((size_t)wide_peak_nd_blocks(c) * kCorrSlab));
         // the regions of a unit are disjoint, so their stretches of 4,096
         // positions number at most positions / 4,096 + 2 per region: the area
         // cannot overflow while the regions fit, and a pass that outgrows
@@ -2671,9 +2593,9 @@ static int launch_pass(up_ctx *c, int slot) {
     const int tl = ps.tl;
     if (tl >= 1) HIPCHK(hipEventRecord(ps.ev[0], s1));
     c->k1a_waves = 0;
-    if (ps.req_q11) {  // K1q: runs of processed positions (threshold <= 0)
+    if (is_q11(scan)) {  // runs of processed positions (threshold <= 0)
         graph = false;
-        const bool wq = c->p.bw > kMaxBw;  // wide K1q (wide_q11_mode)
+        const bool wq = scan == Scan::K1qWide;
         if (!wq) {
             P.peak_pos = nullptr;  // K3 runs its KDE for the peaks
             P.peak_val = nullptr;
@@ -2699,22 +2621,20 @@ static int launch_pass(up_ctx *c, int slot) {
             const unsigned blocks = (unsigned)std::min<uint64_t>((ns + 3) / 4, 4096);
             hipLaunchKernelGGL(proc_runs_kernel, dim3(std::max(1u, blocks)), dim3(256), 0, s1, SP);
         }
-    } else {
-        if (c->p.bw > kMaxBw) {  // K1w: screen + exact in one (wide.hip)
-            graph = false;
-            const unsigned blocks = std::max(1u, std::min<uint32_t>(ns, 8192));
-            with_flag(c->p.nondir != 0, [&](auto nd) {
-                with_pool_mode(pool_mode(c), [&](auto pm) {
-                    hipLaunchKernelGGL((wide_kernel<decltype(pm)::value, decltype(nd)::value>), dim3(blocks),
-                                       dim3(64), 0, s1, SP);
-                });
+    } else if (scan == Scan::K1w) {  // screen + exact in one (wide.hip)
+        graph = false;
+        const unsigned blocks = std::max(1u, std::min<uint32_t>(ns, 8192));
+        with_flag(c->p.nondir != 0, [&](auto nd) {
+            with_pool_mode(pool_mode(c), [&](auto pm) {
+                hipLaunchKernelGGL((wide_kernel<decltype(pm)::value, decltype(nd)::value>), dim3(blocks), dim3(64),
+                                   0, s1, SP);
             });
-        } else {
-            // K1a: stream + screen -- the chunk-sum plane when the index is
-            // on, else the 2-bit fields (one-pass cost: no derived data read)
-            if (plane_scan(c) || window_nh(c->p.bw) > 4) dispatch_scan<false, kModeScreen>(c, s1, SP, 0, ns);
-            else dispatch_scan<false, kModeScreenF>(c, s1, SP, 0, ns);
-        }
+        });
+    } else {
+        // K1a: stream + screen -- the chunk-sum plane when the index is
+        // on, else the 2-bit fields (one-pass cost: no derived data read)
+        if (plane_scan(c) || window_nh(c->p.bw) > 4) dispatch_scan<false, kModeScreen>(c, s1, SP, 0, ns);
+        else dispatch_scan<false, kModeScreenF>(c, s1, SP, 0, ns);
     }
     HIPCHK(hipGetLastError());
     hipEvent_t k1a_end = ps.k1a_end;  // a timed pass's end-of-K1a event serves as well
@@ -2723,9 +2643,8 @@ static int launch_pass(up_ctx *c, int slot) {
     HIPCHK(hipStreamWaitEvent(ps.stream, k1a_end, 0));
     const uint32_t kw = c->k1a_waves, kx = c->k1a_xcap;
     ps.k3_kind = k3_kind_for(c, P, std::max<uint64_t>(ps.req_last_nreg, 1024));  // (dispatch_stats' arguments)
-    const int k1b_kind = (ps.req_q11 || c->p.bw > kMaxBw) ? -1 : k1b_kind_for(c);  // (enqueue_rest's K1b)
+    const int k1b_kind = scan == Scan::K1 ? k1b_kind_for(c) : -1;  // (enqueue_rest's K1b)
     ps.k1b_kind = k1b_kind;
-    ps.scan_kind = ps.req_q11 ? 2 : c->p.bw > kMaxBw ? 1 : 0;  // (the branch taken above)
     if (!graph || tl >= 2) {
         if (int r = enqueue_rest(c, slot, SP, P, cap, kw, kx, tl >= 2)) return r;
         HIPCHK(hipEventRecord(ps.done, ps.stream));
@@ -2796,13 +2715,6 @@ static int launch_pass(up_ctx *c, int slot) {
     return UP_OK;
 }
 
-static int prepare_run(up_ctx *c) {
-    int r = check_runnable(c);
-    if (r) return r;
-    HIPCHK(hipSetDevice(c->dev));
-    return sync_units(c);
-}
-
 static void launcher_main(up_ctx *c) {
     (void)hipSetDevice(c->dev);
     std::unique_lock<std::mutex> lk(c->lmu);
@@ -2843,11 +2755,11 @@ static void launcher_stop(up_ctx *c) {
     c->launcher.join();
 }
 
-int up_run_async(up_ctx *c) {
-    if (!c) return UP_E_ARG;
-    if (c->seq_launched - c->seq_done >= kSlots) return UP_E_STATE;  // at most kSlots passes in flight
-    if (busy(c) && c->units_dirty) return UP_E_STATE;  // passes in flight read the unit table
-    int r = prepare_run(c);
+// enqueue one pass of the context's route (`scan`, never the replay): for
+// up_run_async, and for the blocking up_run whatever Route::async_ok says
+static int enqueue_pass(up_ctx *c, Scan scan) {
+    HIPCHK(hipSetDevice(c->dev));
+    int r = sync_units(c);
     if (r) return r;
     const int slot = (int)(c->seq_launched % kSlots);
     up_ctx::Pass &ps = c->pass[slot];
@@ -2861,8 +2773,8 @@ int up_run_async(up_ctx *c) {
     ps.req_target_hostp = c->target_hostp;
     ps.req_target_cap = c->target_cap;
     ps.req_tl = c->timing;
-    ps.req_q11 = c->q11_run;
-    ps.req_q11_place = c->q11_run && c->q11_place_in_pass;
+    ps.req_scan = scan;
+    ps.req_q11_place = is_q11(scan) && c->q11_place_in_pass;
     ps.req_last_nreg = c->last_nreg;
     ps.req_reg_cap = c->reg_cap;
     ps.req_ovf_cap = c->ovf_cap;
@@ -2892,6 +2804,15 @@ int up_run_async(up_ctx *c) {
     return UP_OK;
 }
 
+int up_run_async(up_ctx *c) {
+    if (!c) return UP_E_ARG;
+    if (c->seq_launched - c->seq_done >= kSlots) return UP_E_STATE;  // at most kSlots passes in flight
+    if (busy(c) && c->units_dirty) return UP_E_STATE;  // passes in flight read the unit table
+    Scan scan;
+    if (int r = check_runnable(c, false, &scan)) return r;
+    return enqueue_pass(c, scan);
+}
+
 // complete the oldest pass in flight
 int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     if (!c) return UP_E_ARG;
@@ -2908,7 +2829,7 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     c->cur_slot = slot;
     c->last_k3_kind = -1;
     c->last_k1b_kind = -1;
-    c->last_scan_kind = -1;
+    c->last_scan.reset();
     if (c->units.empty()) {
         ++c->seq_done;
         if (n_regions) *n_regions = 0;
@@ -2979,10 +2900,10 @@ int up_run_wait(up_ctx *c, uint64_t *n_regions) {
     c->last_nreg = nreg;
     c->last_k3_kind = ps.k3_kind;
     c->last_k1b_kind = ps.k1b_kind;
-    c->last_scan_kind = ps.scan_kind;  // (head units' K0 chains aside)
+    c->last_scan = ps.req_scan;  // (head units' K0 chains aside)
     // (a K1q pass's head units take q11_finish's chains instead)
     int r = UP_OK;
-    if (ps.req_q11) {
+    if (is_q11(ps.req_scan)) {
         // (nothing here: q11_finish's chains take its head units)
     } else if (ps.head_place && !(c->hp_status[slot].p[kHeadStErr] & kHeadK0Bad)) {
         // replayed and merged inside the pass: the slot holds the final list
@@ -3115,7 +3036,7 @@ static int replay_segments(up_ctx *c, std::vector<up_region> &emu, std::vector<u
     return UP_OK;
 }
 
-// every unit through K0 (replay_mode configurations): the segmented replay,
+// every unit through K0 (Scan::Replay configurations): the segmented replay,
 // or -- with the -w capture on (its retirements must keep each unit's add
 // order) or UNIPEAK_REPLAY_WHOLE=1 -- one chain per buffer, never resynced
 static int run_replay(up_ctx *c, uint64_t *n_regions) {
@@ -3129,7 +3050,8 @@ static int run_replay(up_ctx *c, uint64_t *n_regions) {
     c->last_head_kind = -1;
     c->last_k3_kind = -1;  // K0 computes the replay's statistics
     c->last_k1b_kind = -1;
-    c->last_scan_kind = c->units.empty() ? -1 : 3;
+    c->last_scan.reset();
+    if (!c->units.empty()) c->last_scan = Scan::Replay;
     c->h_regions.clear();
     c->h_counts.clear();
     c->h_emulated.clear();
@@ -3157,7 +3079,7 @@ static int run_replay(up_ctx *c, uint64_t *n_regions) {
         }();
         // (the segmented replay's chains assume a window drained after 2bw + 1
         // positions without an add: false from bw 32,768 on, where the
-        // reference's UShort retirement count wraps -- wide_mode)
+        // reference's UShort retirement count wraps -- route.h)
         if (!c->prof_capture && kTB == 2 && !whole && c->p.bw <= kMaxWideBw) {
             if ((r = replay_segments(c, emu, ecnt, soff, order))) return r;
             c->h_resync.assign(nu, 0);
@@ -3346,12 +3268,10 @@ static int q11_finish(up_ctx *c, const std::vector<uint32_t> *heads) {
     return UP_OK;
 }
 
-static int run_replay(up_ctx *c, uint64_t *n_regions);
-
-// threshold <= 0 (q11_mode): one K1q pass; units that process position 1
+// threshold <= 0 (Scan::K1q, Scan::K1qWide): one pass; units that process position 1
 // (an add at <= bw + 1) add the chains of the exact replay around them
 // (q11_finish).  With the -w capture on, the whole-buffer replay instead.
-static int run_q11(up_ctx *c, uint64_t *n_regions) {
+static int run_q11(up_ctx *c, Scan scan, uint64_t *n_regions) {
     HIPCHK(hipSetDevice(c->dev));
     int r = sync_units(c);
     if (r) return r;
@@ -3367,18 +3287,15 @@ static int run_q11(up_ctx *c, uint64_t *n_regions) {
         HIPCHK(hipMemcpyAsync(f.data(), c->d_q11_head.p, nu * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         for (uint32_t v : f) any |= v != 0;
-        if (any && (c->prof_capture || q11_whole_replay())) return run_replay(c, n_regions);
+        if (any && (c->prof_capture || c->sw.q11_heads_replay)) return run_replay(c, n_regions);
         std::vector<int32_t> ub(nu);  // the placement's buffer column
         for (uint32_t i = 0; i < nu; ++i) ub[i] = c->units[i].buffer;
         HIPCHK(c->d_unit_buffer.ensure(nu));
         HIPCHK(hipMemcpy(c->d_unit_buffer.p, ub.data(), nu * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    c->q11_run = true;
     c->q11_place_in_pass = !any;
-    r = up_run_async(c);
-    if (!r) r = up_run_wait(c, nullptr);
-    c->q11_run = false;
-    if (r) return r;
+    if ((r = enqueue_pass(c, scan))) return r;
+    if ((r = up_run_wait(c, nullptr))) return r;
     const auto t0 = std::chrono::steady_clock::now();
     if ((r = q11_finish(c, any ? &f : nullptr))) return r;
     c->times[3] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -3386,26 +3303,14 @@ static int run_q11(up_ctx *c, uint64_t *n_regions) {
     return UP_OK;
 }
 
-// K1w over a nondirectional context: one blocking pass (check_runnable
-// admits it only here)
-static int run_wide_nd(up_ctx *c, uint64_t *n_regions) {
-    c->wide_nd_run = true;
-    int r = up_run_async(c);
-    if (!r) r = up_run_wait(c, n_regions);
-    c->wide_nd_run = false;
-    return r;
-}
-
 int up_run(up_ctx *c, uint64_t *n_regions) {
     if (!c) return UP_E_ARG;
     if (busy(c)) return UP_E_STATE;
-    int rc = check_params(c);
-    if (rc) return rc;
-    if (replay_mode(c)) return run_replay(c, n_regions);
-    if (q11_mode(c)) return run_q11(c, n_regions);
-    if (wide_nd_mode(c)) return run_wide_nd(c, n_regions);
-    int r = up_run_async(c);
-    if (r) return r;
+    if (int rc = check_params(c)) return rc;
+    const Scan scan = route_of(c).scan;
+    if (scan == Scan::Replay) return run_replay(c, n_regions);
+    if (is_q11(scan)) return run_q11(c, scan, n_regions);
+    if (int r = enqueue_pass(c, scan)) return r;
     return up_run_wait(c, n_regions);
 }
 
@@ -3573,7 +3478,7 @@ static int shift_run(up_ctx *c, const uint64_t *idx, size_t n, uint16_t max_shif
     // (the last pass ran K1w or wide K1q: K4's own KDE spans NH <= 8 window words, so
     // wide_fill_kernel forms the scores of its regions into the slab first --
     // mark 2; head-replayed regions keep their stored scores)
-    const bool wide = c->last_scan_kind == 1 || (c->last_scan_kind == 2 && c->p.bw > kMaxBw);  // (nondirectional: checked above)
+    const bool wide = c->last_scan && is_wide(*c->last_scan);
     bool any_fill = false;
     std::vector<uint64_t> off(n, 0);
     std::vector<uint8_t> pref(n + 1, 0);
@@ -3664,16 +3569,13 @@ int up_timings(up_ctx *c, double *ms, int n) {
 // of the call, on the context's stream (not waited for): *d_f, and *d_r four-
 // position aligned behind it, both zero-filled up to a multiple of four
 // positions.  The checks of up_unit_profile_range that do not concern its
-// output arrays; up_timings [5] once the caller has drained the stream
-// (profile_dense_time).
+// output arrays, check_runnable and busy aside (the entry point's); up_timings [5]
+// once the caller has drained the stream (profile_dense_time).
 static int profile_dense(up_ctx *c, uint32_t unit, uint64_t first, uint32_t count, StreamScratch &scratch,
                          double **d_f, double **d_r) {
-    int r = check_runnable(c, true);
-    if (r) return r;
-    if (busy(c)) return UP_E_STATE;  // a pass in flight reads this state
     if (unit >= c->units.size() || first < 1 || count == 0) return UP_E_ARG;
     HIPCHK(hipSetDevice(c->dev));
-    if ((r = sync_units(c))) return r;
+    if (int r = sync_units(c)) return r;
     const Unit &u = c->units[unit];
     const uint64_t dom = (uint64_t)u.nstrips * kStrip;  // scan domain incl. Q16 tail
     if (first + count - 1 > dom) return UP_E_ARG;
@@ -3688,13 +3590,12 @@ static int profile_dense(up_ctx *c, uint32_t unit, uint64_t first, uint32_t coun
     P.prof_len = count;
     P.prof_unit = unit;
     HIPCHK(hipEventRecord(c->ev[5], c->stream));
-    if (c->p.bw > kMaxBw) {  // wide_mode (check_runnable): the planes are current (want_index)
+    if (is_wide(route_of(c).scan)) {  // the planes are current (want_index)
         const uint32_t cap = wide_list_cap();
         const uint64_t nstretch = ((first + count - 2) / 64 - (first - 1) / 64) / kProfWords + 1;
         const dim3 grid((unsigned)std::min<uint64_t>(nstretch, 1u << 16));
         const size_t lds = prof_lds_bytes(c->p.bw);
-        // (nondirectional: f and r, each its own ascending sum -- up_set_wide_nd_full or
-        // up_set_wide_q11_nd: check_runnable)
+        // (nondirectional: f and r, each its own ascending sum)
         with_flag(c->p.nondir != 0, [&](auto nd) {
             with_pool_mode(pool_mode(c), [&](auto pm) {
                 hipLaunchKernelGGL((wide_profile_kernel<decltype(pm)::value, decltype(nd)::value>), grid, dim3(64),
@@ -3721,12 +3622,13 @@ static void profile_dense_time(up_ctx *c) {
 
 int up_unit_profile_range(up_ctx *c, uint32_t unit, uint64_t first, uint32_t count, double *out_f,
                           double *out_r) {
-    int r = check_runnable(c, true);
+    Scan scan;
+    int r = check_runnable(c, true, &scan);
     if (r) return r;
     if (busy(c)) return UP_E_STATE;
     if (!out_f) return UP_E_ARG;
-    // both strands' scores are the answer (K1w, or wide K1q behind up_set_wide_q11_nd)
-    if (!out_r && c->p.nondir && c->p.bw > kMaxBw) return UP_E_ARG;
+    // both strands' scores are the answer
+    if (!out_r && c->p.nondir && is_wide(scan)) return UP_E_ARG;
     StreamScratch scratch(c->stream);
     double *d_f = nullptr, *d_r = nullptr;
     if ((r = profile_dense(c, unit, first, count, scratch, &d_f, &d_r))) return r;
