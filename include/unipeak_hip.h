@@ -318,6 +318,46 @@ int up_shift_best(up_ctx *ctx, const uint64_t *region_idx, size_t n,
 int up_set_index_policy(up_ctx *ctx, int policy);
 int up_invalidate_index(up_ctx *ctx);
 int up_index_state(up_ctx *ctx, int *on, uint64_t *builds);
+/* Read-only view of one unit's index, for tests and tools; on no pass's
+ * path.  Both calls first settle the passes in flight and bring the unit
+ * table and the index up to date exactly as the next pass would (so under
+ * UP_INDEX_ALWAYS, or where the next pass is a wide one, a stale index is
+ * built and counted in up_index_state's builds); they change nothing else.
+ * up_unit_layout: the geometry of the unit's arrays -- stride = bytes per
+ * track (a multiple of 256), pad_pos = zero positions in front of position 1
+ * (position p is field pad_pos + p - 1), track_bits = up_track_bits(),
+ * index_on as up_index_state reports it, has_pooled = the pooled plane is
+ * kept (nondirectional units, several pooled samples or coefficients; no
+ * kernel reads it otherwise), has_pct = the unit holds a pooled count track.
+ * up_unit_index_read copies one array to host memory as it lies on the
+ * device (csrc/kernels.h describes the bytes), ntracks = nstrands * n_samples,
+ * track (strand, sample) at index strand * n_samples + sample:
+ *   UP_IDX_TRACKS  the packed tracks, ntracks * stride bytes
+ *   UP_IDX_CSUM    the chunk-sum planes, ntracks * stride / 4 bytes
+ *   UP_IDX_POOLED  the unit's pooled plane, stride / 4 bytes
+ *   UP_IDX_PCT     the pooled count track, nstrands * 4 * stride bytes
+ * *n (optional) = the array's size, also when cap is too small.  UP_E_STATE:
+ * no parameters yet, the index is not on after the sync (UP_INDEX_NEVER, the
+ * first pass under UP_INDEX_AUTO, 4-bit tracks), UP_IDX_POOLED without
+ * has_pooled, or UP_IDX_PCT without has_pct; UP_E_ARG: unit out of range, an unknown
+ * `what`, dst = NULL, or cap below the array's size. */
+typedef struct up_unit_layout_t {
+    uint64_t stride;
+    uint32_t len;
+    int32_t nstrands;
+    int32_t n_samples;
+    int32_t pad_pos;
+    int32_t track_bits;
+    int32_t index_on;
+    int32_t has_pooled;
+    int32_t has_pct;
+} up_unit_layout_t;
+#define UP_IDX_TRACKS 0
+#define UP_IDX_CSUM 1
+#define UP_IDX_POOLED 2
+#define UP_IDX_PCT 3
+int up_unit_layout(up_ctx *ctx, uint32_t unit, up_unit_layout_t *out);
+int up_unit_index_read(up_ctx *ctx, uint32_t unit, int what, void *dst, uint64_t cap, uint64_t *n);
 /* which statistics kernel (K3) the pass completed last (up_run, up_run_wait)
  * was launched with: 0 the general kernel, 1 the batched kernel for one
  * directional sample with a wave per region, 2 the same with a lane per

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UNIPEAK_LIB") or os.path.join(_HERE, "lib", "libunipeak_hip.so")
 
 UP_OK = 0
-UP_E_NOMEM, UP_E_STATE = -3, -4  # (include/unipeak_hip.h)
+UP_E_ARG, UP_E_NOMEM, UP_E_STATE = -1, -3, -4  # (include/unipeak_hip.h)
 MAX_IN_FLIGHT = 5  # UP_MAX_IN_FLIGHT (include/unipeak_hip.h)
 
 
@@ -73,7 +73,8 @@ EXPORTS = [
     "up_timings", "up_scan_density", "up_unit_profile", "up_hbm_copy_gbps", "up_set_record_target",
     "up_host_register", "up_unit_profile_range", "up_unit_profile_text", "up_unit_profile_bigwig", "up_run_async", "up_run_wait", "up_set_timing",
     "up_set_profile_capture", "up_unit_replay_profile", "up_set_wide_nd_full",
-    "up_set_index_policy", "up_invalidate_index", "up_index_state", "up_last_stats_kind", "up_last_exact_kind",
+    "up_set_index_policy", "up_invalidate_index", "up_index_state", "up_unit_layout", "up_unit_index_read",
+    "up_last_stats_kind", "up_last_exact_kind",
     "up_last_scan_kind", "up_set_head_place", "up_last_head_kind",
     "up_tir_open", "up_tir_close", "up_tir_set_stream", "up_tir_query", "up_tir_timings",
     "up_cm_open", "up_cm_close", "up_cm_add", "up_cm_collect", "up_cm_timings",
@@ -85,6 +86,21 @@ EXPORTS = [
 # letters and underscores only)
 TIR_HOST = 0xFFFFFFFF  # UP_TIR_HOST
 INDEX_AUTO, INDEX_NEVER, INDEX_ALWAYS = 0, 1, 2  # UP_INDEX_*
+IDX_TRACKS, IDX_CSUM, IDX_POOLED, IDX_PCT = 0, 1, 2, 3  # UP_IDX_*
+
+
+class UnitLayout(ctypes.Structure):  # up_unit_layout_t
+    _fields_ = [
+        ("stride", ctypes.c_uint64),
+        ("len", ctypes.c_uint32),
+        ("nstrands", ctypes.c_int32),
+        ("n_samples", ctypes.c_int32),
+        ("pad_pos", ctypes.c_int32),
+        ("track_bits", ctypes.c_int32),
+        ("index_on", ctypes.c_int32),
+        ("has_pooled", ctypes.c_int32),
+        ("has_pct", ctypes.c_int32),
+    ]
 
 
 def load_library(path=LIB_PATH):
@@ -137,6 +153,8 @@ def load_library(path=LIB_PATH):
         "up_set_index_policy": (c.c_int, [vp, c.c_int]),
         "up_invalidate_index": (c.c_int, [vp]),
         "up_index_state": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_uint64)]),
+        "up_unit_layout": (c.c_int, [vp, c.c_uint32, c.POINTER(UnitLayout)]),
+        "up_unit_index_read": (c.c_int, [vp, c.c_uint32, c.c_int, vp, c.c_uint64, c.POINTER(c.c_uint64)]),
         "up_last_stats_kind": (c.c_int, [vp]),
         "up_last_exact_kind": (c.c_int, [vp]),
         "up_last_scan_kind": (c.c_int, [vp]),
@@ -427,6 +445,27 @@ class Lib:
         on, b = ctypes.c_int(0), ctypes.c_uint64(0)
         _ck(self.L.up_index_state(self.ctx, ctypes.byref(on), ctypes.byref(b)))
         return bool(on.value), int(b.value)
+
+    def unit_layout(self, unit):
+        """the geometry of a unit's tracks and index arrays as a UnitLayout, after the
+        sync a pass would run (up_unit_layout)"""
+        lay = UnitLayout()
+        _ck(self.L.up_unit_layout(self.ctx, unit, ctypes.byref(lay)))
+        return lay
+
+    def index_read(self, unit, what):
+        """one of a unit's arrays as it lies on the device, a numpy.uint8 array: IDX_TRACKS,
+        IDX_CSUM, IDX_POOLED or IDX_PCT; builds a stale index first, as the next pass would
+        (up_unit_index_read)"""
+        lay = self.unit_layout(unit)
+        ntracks = lay.nstrands * lay.n_samples
+        size = {IDX_TRACKS: ntracks * lay.stride, IDX_CSUM: ntracks * (lay.stride // 4),
+                IDX_POOLED: lay.stride // 4, IDX_PCT: lay.nstrands * 4 * lay.stride}.get(what, 1)
+        out = np.zeros(size, np.uint8)
+        n = ctypes.c_uint64(0)
+        _ck(self.L.up_unit_index_read(self.ctx, unit, int(what), out.ctypes.data, out.size, ctypes.byref(n)))
+        assert n.value == out.size, (n.value, out.size)
+        return out
 
     def last_k3_kind(self):
         """K3 of the pass completed last: 0 general, 1 a wave per region, 2 a lane

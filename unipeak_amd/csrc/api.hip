@@ -1375,6 +1375,52 @@ static int sync_units(up_ctx *c) {
     return sync_index(c);
 }
 
+// the index as the next pass would find it: passes in flight settled, then
+// the pass's own sync_units (up_unit_layout, up_unit_index_read)
+static int sync_for_read(up_ctx *c, uint32_t unit) {
+    if (!c || unit >= c->units.size()) return UP_E_ARG;
+    if (!c->have_params) return UP_E_STATE;
+    HIPCHK(hipSetDevice(c->dev));
+    if (busy(c)) settle_in_flight(c);
+    return sync_units(c);
+}
+
+int up_unit_layout(up_ctx *c, uint32_t unit, up_unit_layout_t *out) {
+    if (!out) return UP_E_ARG;
+    if (int r = sync_for_read(c, unit)) return r;
+    const Unit &u = c->units[unit];
+    *out = up_unit_layout_t{};
+    out->stride = u.stride;
+    out->len = u.len;
+    out->nstrands = u.nstrands;
+    out->n_samples = c->p.n_samples;
+    out->pad_pos = kPadPos;
+    out->track_bits = kTB;
+    out->index_on = c->index_on ? 1 : 0;
+    out->has_pooled = c->index_on && (c->p.nondir || pool_mode(c) != 0) ? 1 : 0;
+    out->has_pct = c->index_on && u.d_pct.p ? 1 : 0;
+    return UP_OK;
+}
+
+int up_unit_index_read(up_ctx *c, uint32_t unit, int what, void *dst, uint64_t cap, uint64_t *n) {
+    if (!dst || what < UP_IDX_TRACKS || what > UP_IDX_PCT) return UP_E_ARG;
+    if (int r = sync_for_read(c, unit)) return r;
+    const Unit &u = c->units[unit];
+    const bool pooled = c->p.nondir || pool_mode(c) != 0;  // (sync_index keeps the pooled plane then)
+    if (!c->index_on || (what == UP_IDX_POOLED && !pooled) || (what == UP_IDX_PCT && !u.d_pct.p)) return UP_E_STATE;
+    const uint64_t ntracks = (uint64_t)u.nstrands * c->p.n_samples;
+    const uint8_t *src = u.dptr.p;  // tracks | chunk-sum planes | pooled plane (kernels.h)
+    uint64_t bytes = ntracks * u.stride;
+    if (what == UP_IDX_CSUM) { src += ntracks * u.stride; bytes = ntracks * (u.stride / 4); }
+    if (what == UP_IDX_POOLED) { src += ntracks * u.stride / 4 * 5; bytes = u.stride / 4; }
+    if (what == UP_IDX_PCT) { src = u.d_pct.p; bytes = (uint64_t)u.nstrands * kPerByte * u.stride; }
+    if (n) *n = bytes;
+    if (cap < bytes) return UP_E_ARG;
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return UP_OK;
+}
+
 // 0: one non-control sample; 1: several, summed in uint32 window words
 // (kernels.hip WinT) -- only while no position's sum can reach 2^32, else
 // 2 with zero coefficients (d_coef), the FP64 pooling of -z (quirk Q5)
