@@ -1666,7 +1666,7 @@ static int k3_kind_for(const up_ctx *c, const StatParams &P, uint64_t nreg) {
 static void dispatch_stats(up_ctx *c, hipStream_t st, const StatParams &P, uint64_t nreg) {
     const int kind = k3_kind_for(c, P, nreg);
     // (beyond 256 samples one LDS row of exptSums per wave, kernels.hip add_es)
-    const size_t lds = kind == 2 ? kStat1LLds : kind == 1 ? kStat1Lds
+    const size_t lds = kind == 2 ? stat1l_lds(P.bw) : kind == 1 ? kStat1Lds
                                                           : kStatLds + (c->p.n_samples > 256 ? 4 * 4 * (size_t)c->p.n_samples : 0);
     const void *k = stats_kernel_for(P.bw, pool_mode(c), c->p.nondir != 0, kind);
     uint64_t cap = resident_blocks(c, k, lds, kind == 2 ? kK3LThreads : 256);

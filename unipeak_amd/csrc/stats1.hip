@@ -381,20 +381,45 @@ constexpr int kK3LRecWords = 7;  // 56-byte up_region as uint64 words
 constexpr int kK3LRow = 32;      // region dwords staged per lane at a time (512 positions)
 constexpr int kK3LEsc = 64;      // escaped counts cached per lane (bytes)
 constexpr int kK3LRowStride = kK3LRow + 1;  // (odd: the lanes' k-th words fall in distinct banks)
-constexpr int kK3LThreads = 128; // two waves per block (the per-lane LDS rows)
-constexpr size_t kStat1LLds = kKTab * sizeof(double) + (kK3LThreads / 64) * 64 * kK3LRecWords * sizeof(uint64_t) +
-                              kK3LThreads * (kK3LRowStride * sizeof(uint32_t) + kK3LEsc);
+constexpr int kK3LBatch = 16;    // of them loaded at once (the row is filled in kK3LRow / kK3LBatch steps)
+// four waves per workgroup, one per SIMD (-DUPK_K3L_THREADS=128: the two-wave
+// shape of round 6, for A/B builds; profiles/k3l_fit/README.md)
+#ifndef UPK_K3L_THREADS
+#define UPK_K3L_THREADS 256
+#endif
+constexpr int kK3LThreads = UPK_K3L_THREADS;  // waves per block x 64 (the per-lane LDS rows)
+static_assert(kK3LThreads % 64 == 0 && kK3LRow % kK3LBatch == 0 && kK3LRow <= 32, "whole waves, whole batches, one mask");
+// dynamic LDS of a workgroup: the padded weight table sized for the pass's
+// bandwidth (as exact1_lds: an even number of doubles, so the areas behind
+// stay 16-byte aligned), the waves' record stages, the lanes' rows and
+// escape caches
+__host__ __device__ constexpr int stat1l_ktab(int bw) { return 2 * kKPad + 2 * bw + 2; }
+inline size_t stat1l_lds(int bw) {
+    return (size_t)stat1l_ktab(bw) * sizeof(double) + (kK3LThreads / 64) * 64 * kK3LRecWords * sizeof(uint64_t) +
+           kK3LThreads * (kK3LRowStride * sizeof(uint32_t) + kK3LEsc);
+}
 
+#ifdef UPK_K3L_WPE  // (A/B builds: at most 512 / UPK_K3L_WPE registers per lane, spilling the rest)
+#define UPK_K3L_OCC __attribute__((amdgpu_waves_per_eu(UPK_K3L_WPE)))
+#else
+#define UPK_K3L_OCC
+#endif
 template <int NH>
-__global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
+__global__ void __launch_bounds__(kK3LThreads) UPK_K3L_OCC stats1L_kernel(StatParams P) {
     extern __shared__ double lds_[];
     const int bw = P.bw;
-    const double *ktab = load_ktab(lds_, P.kern, bw);
-    uint64_t *rstage = (uint64_t *)(lds_ + kKTab) + (threadIdx.x >> 6) * 64 * kK3LRecWords;
+    const int ktab_n = stat1l_ktab(bw);
+    for (int i = threadIdx.x; i < ktab_n; i += blockDim.x) {
+        const int j = i - kKPad;
+        lds_[i] = (j >= 0 && j <= 2 * bw) ? P.kern[j] : 0.0;
+    }
+    __syncthreads();
+    const double *ktab = lds_ + kKPad;
+    uint64_t *rstage = (uint64_t *)(lds_ + ktab_n) + (threadIdx.x >> 6) * 64 * kK3LRecWords;
     // this lane's staged region dwords and escaped counts
-    uint32_t *row = (uint32_t *)((uint64_t *)(lds_ + kKTab) + (kK3LThreads / 64) * 64 * kK3LRecWords) +
+    uint32_t *row = (uint32_t *)((uint64_t *)(lds_ + ktab_n) + (kK3LThreads / 64) * 64 * kK3LRecWords) +
                     threadIdx.x * kK3LRowStride;
-    uint8_t *ecache = (uint8_t *)((uint32_t *)((uint64_t *)(lds_ + kKTab) + (kK3LThreads / 64) * 64 * kK3LRecWords) +
+    uint8_t *ecache = (uint8_t *)((uint32_t *)((uint64_t *)(lds_ + ktab_n) + (kK3LThreads / 64) * 64 * kK3LRecWords) +
                                   kK3LThreads * kK3LRowStride) +
                       threadIdx.x * kK3LEsc;
     constexpr int NWT = 2 * NH + 1;
@@ -402,12 +427,17 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
     const uint64_t nreg = *P.nreg < P.cap ? *P.nreg : P.cap;
-    uint64_t wm[NWT];
-#pragma unroll
-    for (int d = -NH; d <= NH; ++d) wm[d + NH] = win_mask(d, bw);
     const int nc0 = P.nc[0];
     const uint32_t trk = (uint32_t)nc0;
     const bool ctl0 = P.is_control[0] != 0;
+    // Registers (DESIGN.md §4 "K3L beside K1a"): a lane keeps of its unit the
+    // track pointer, the escape tiles' pointer and two tile indices; the
+    // whole descriptor is read again where a rare path needs it (an escape
+    // outside the two tiles or above 254, a run across a strip edge).  A
+    // track's dwords are indexed in 32 bits from the track: dword
+    // kPadPos / 16 + (p - 1) / 16 holds position p, below 2^29 for any p.
+    constexpr uint32_t kPadDw = kPadPos / 16;
+    static_assert(kPadPos % 16 == 0, "position 1 is field 0 of a dword");
 
     for (uint64_t base = (uint64_t)wave * 64; base < nreg; base += (uint64_t)nwaves * 64) {
         const uint64_t ri = base + (uint64_t)lane;
@@ -416,12 +446,18 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
         const uint32_t left = P.starts[rq], right = P.ends[rq], u = P.reg_unit[rq];
         uint32_t kpos = P.peak_pos[rq];
         double kval = P.peak_val[rq];
-        const UnitDesc U = P.units[u];
-        gu32 *tw = (gu32 *)((gu8 *)U.base + (uint64_t)nc0 * U.stride);
+        const UnitDesc *Up = P.units + u;
+        gu32 *tw = (gu32 *)((gu8 *)Up->base + (uint64_t)nc0 * Up->stride);
+        // an escaped count through the whole descriptor (rare: see above)
+        auto lookup = [&](uint32_t pos) -> uint32_t {
+            const UnitDesc Ue = *Up;
+            return ovf_lookup(Ue, trk, pos);
+        };
         if (kpos == 0) {  // the run crossed a strip edge: its parts, in position order
-            const uint32_t sa = U.strip0 + (left - 1) / kStrip, sb = U.strip0 + (right - 1) / kStrip;
+            const uint32_t strip0 = Up->strip0;
+            const uint32_t sa = strip0 + (left - 1) / kStrip, sb = strip0 + (right - 1) / kStrip;
             for (uint32_t s = sa; s <= sb; ++s) {
-                const uint32_t sp0 = 1 + (s - U.strip0) * kStrip;
+                const uint32_t sp0 = 1 + (s - strip0) * kStrip;
                 const bool prt = (s > sa || left == sp0) && s == sb && right < sp0 + kStrip - 1;
                 const uint64_t *e = P.spk + 4ull * s + (prt ? 0 : 2);
                 const double v = __longlong_as_double((long long)e[0]);
@@ -441,33 +477,41 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
         }
         const bool kn = !(P.qmode && kval != __builtin_floor(kval));
         if (P.cut == 1) continue;  // (measurement aid: descriptors only)
-        // fields of dword j restricted to positions [left, right]
-        const int64_t n0 = kPadPos + (int64_t)left - 1, n1 = kPadPos + (int64_t)right - 1;
-        const int64_t j0 = n0 >> 4, j1 = n1 >> 4;
-        auto dword_at = [&](int64_t j) -> uint32_t {
-            uint32_t d = tw[j];
-            if (j == j0) d &= ~0u << (2 * (n0 & 15));
-            if (j == j1 && (n1 & 15) != 15) d &= (1u << (2 * ((n1 & 15) + 1))) - 1u;
-            return d;
-        };
-        // dwords c0 .. min(c0 + kK3LRow - 1, c1) of the fields [f0, f1] into
-        // the lane's row; returns the mask of the nonzero ones.  Every load
-        // is unconditional (indices clamped) and lands in registers before
-        // the row is written: loads guarded one by one and stored at once
-        // compiled to one wait per dword (the first K3L measured 0.22 ms)
-        auto stage = [&](int64_t c0, int64_t c1, int64_t f0, int64_t f1) -> uint32_t {
-            uint32_t v[kK3LRow];
-#pragma unroll
-            for (int k = 0; k < kK3LRow; ++k) v[k] = tw[c0 + k <= c1 ? c0 + k : c1];
+        // (dword, field) of the region's first and last position
+        const uint32_t j0 = kPadDw + ((left - 1u) >> 4), j1 = kPadDw + ((right - 1u) >> 4);
+        const uint32_t f0 = (left - 1u) & 15u, f1 = (right - 1u) & 15u;
+        // dwords c0 .. min(c0 + kK3LRow - 1, c1) into the lane's row, cut to
+        // the fields from fa of dword ja to fb of dword jb; returns the mask
+        // of the nonzero ones.  Every load of a batch is unconditional
+        // (indices clamped) and lands in registers before the row is
+        // written: loads guarded one by one and stored at once compiled to
+        // one wait per dword (the first K3L measured 0.22 ms).  A batch is
+        // kK3LBatch dwords -- the whole row at once held 32 loaded dwords
+        // and their addresses -- and a batch that no lane of the wave needs
+        // is skipped (its row words are never read: the mask has no bit for
+        // them, and the wave's path reads a row up to the region's last
+        // dword only)
+        auto stage = [&](uint32_t c0, uint32_t c1, uint32_t ja, uint32_t fa, uint32_t jb, uint32_t fb) -> uint32_t {
             uint32_t m = 0;
 #pragma unroll
-            for (int k = 0; k < kK3LRow; ++k) {
-                const int64_t j = c0 + k;
-                uint32_t d = j <= c1 ? v[k] : 0u;
-                if (j == (f0 >> 4)) d &= ~0u << (2 * (f0 & 15));
-                if (j == (f1 >> 4) && (f1 & 15) != 15) d &= (1u << (2 * ((f1 & 15) + 1))) - 1u;
-                row[k] = d;
-                m |= (d != 0u ? 1u : 0u) << k;
+            for (int h = 0; h < kK3LRow; h += kK3LBatch) {
+                if (h > 0 && __ballot(c0 + (uint32_t)h <= c1) == 0) break;
+                uint32_t v[kK3LBatch];
+#pragma unroll
+                for (int k = 0; k < kK3LBatch; ++k) {
+                    const uint32_t j = c0 + (uint32_t)(h + k);
+                    v[k] = tw[j <= c1 ? j : c1];
+                }
+#pragma unroll
+                for (int k = 0; k < kK3LBatch; ++k) {
+                    const uint32_t j = c0 + (uint32_t)(h + k);
+                    uint32_t d = j <= c1 ? v[k] : 0u;
+                    if (j == ja) d &= ~0u << (2 * fa);
+                    if (j == jb && fb != 15u) d &= (1u << (2 * (fb + 1u))) - 1u;
+                    row[h + k] = d;
+                    m |= (d != 0u ? 1u : 0u) << (h + k);
+                }
+                __builtin_amdgcn_sched_barrier(0);  // (the next batch's loads stay behind this one's stores)
             }
             return m;
         };
@@ -482,27 +526,27 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
         // caches the counts (kK3LEsc per lane) for the second.
         const int nd = (int)(j1 - j0 + 1);
         const bool staged = nd <= kK3LRow;
-        const uint32_t nzm = (live && staged) ? stage(j0, j1, n0, n1) : 0u;
+        const uint32_t nzm = (live && staged) ? stage(j0, j1, j0, f0, j1, f1) : 0u;
         auto walk = [&](bool cache, auto &&visit) {
             uint32_t ne = 0;  // escaped fields so far
-            auto one = [&](uint32_t &d, int64_t j) {
+            auto one = [&](uint32_t &d, uint32_t j) {
                 const int b = __builtin_ctz(d) & ~1;  // the field's low bit
                 uint32_t c = (d >> b) & 3u;
                 d &= ~(3u << b);
-                const int64_t pos = 16 * j + b / 2 - kPadPos + 1;
+                const uint32_t pos = 16u * (j - kPadDw) + (uint32_t)(b / 2) + 1u;
                 if (c == kEsc) {
                     if (cache && ne < (uint32_t)kK3LEsc && ecache[ne] != 255u) {
                         c = ecache[ne];
                     } else {
-                        c = ovf_lookup(U, trk, (uint32_t)pos);
+                        c = lookup(pos);
                         if (!cache && ne < (uint32_t)kK3LEsc) ecache[ne] = (uint8_t)(c < 255u ? c : 255u);
                     }
                     ++ne;
                 }
-                visit((uint32_t)pos, c);
+                visit(pos, c);
             };
             // the hits of the staged chunk starting at dword c0 (mask m)
-            auto hits = [&](uint32_t m, int64_t c0) {
+            auto hits = [&](uint32_t m, uint32_t c0) {
                 uint32_t d = 0;
                 int k = 0;
                 for (;;) {
@@ -512,7 +556,7 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
                         m &= m - 1u;
                         d = row[k];
                     }
-                    one(d, c0 + k);
+                    one(d, c0 + (uint32_t)k);
                 }
             };
             if (staged) {
@@ -521,18 +565,20 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
                 // longer regions: kK3LRow dwords at a time, each chunk's
                 // loads in flight together (one dependent load per dword
                 // made the longest region of any wave the kernel's time)
-                for (int64_t c0 = j0; c0 <= j1; c0 += kK3LRow) hits(stage(c0, j1, n0, n1), c0);
+                for (uint32_t c0 = j0; c0 <= j1; c0 += kK3LRow) hits(stage(c0, j1, j0, f0, j1, f1), c0);
             }
         };
         if (P.cut == 2) continue;  // (+ staging)
         constexpr uint32_t kLo = 0x55555555u;
         // the escape tiles of the region's first two overflow blocks (a
         // staged region spans at most two; longer ones may look up more)
-        const uint32_t nblk = ovf_nblk(U.len), b0 = (left - 1u) >> kOvfBlkShift;
-        const bool has_ovf = U.ovf != 0;
+        const uint32_t b0 = (left - 1u) >> kOvfBlkShift;
+        const bool has_ovf = Up->ovf != 0;
+        gu8 *tiles = (gu8 *)Up->ovf_tiles;
         uint32_t ti0 = kNoTile, ti1 = kNoTile;
         if (live && has_ovf) {
-            gu32 *tix = (gu32 *)U.ovf_tidx + (size_t)trk * nblk;
+            const uint32_t nblk = ovf_nblk(Up->len);
+            gu32 *tix = (gu32 *)Up->ovf_tidx + (size_t)trk * nblk;
             ti0 = tix[b0];
             ti1 = tix[b0 + 1u < nblk ? b0 + 1u : b0];
         }
@@ -546,13 +592,13 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
             // replaces it, and is cached for the second walk.
             constexpr uint32_t kFb[4] = {0x44444444u, 0x50505050u, 0x55005500u, 0x55550000u};
             uint32_t ne = 0;
-            auto moments = [&](uint32_t m, int64_t c0) {
+            auto moments = [&](uint32_t m, uint32_t c0) {
                 uint32_t em = 0;  // dwords holding an escaped field
                 while (m) {
                     const int k = __builtin_ctz(m);
                     m &= m - 1u;
                     const uint32_t d = row[k];
-                    const uint32_t off = (uint32_t)(16 * (c0 + k) - kPadPos + 1) - left;  // field 0's offset
+                    const uint32_t off = 16u * (c0 + (uint32_t)k - kPadDw) + 1u - left;  // field 0's offset
                     const uint32_t s = __builtin_popcount(d & kLo) + 2u * __builtin_popcount(d & ~kLo);
                     uint32_t w = 0;
 #pragma unroll
@@ -577,10 +623,10 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
                         ok[i] = em != 0u;
                         ks[i] = ok[i] ? __builtin_ctz(em) : ks[0];
                         em &= em - 1u;
-                        const uint32_t p1 = (uint32_t)(16 * (c0 + ks[i]) - kPadPos);  // field 0's position - 1
+                        const uint32_t p1 = 16u * (c0 + (uint32_t)ks[i] - kPadDw);  // field 0's position - 1
                         const uint32_t blk = p1 >> kOvfBlkShift;
                         const uint32_t ti = blk == b0 ? ti0 : blk == b0 + 1u ? ti1 : kNoTile;
-                        src[i] = ti != kNoTile ? (gu8 *)U.ovf_tiles + (size_t)ti * kOvfBlk + (p1 & (kOvfBlk - 1u))
+                        src[i] = ti != kNoTile ? tiles + (size_t)ti * kOvfBlk + (p1 & (kOvfBlk - 1u))
                                                : (gu8 *)P.kern;  // (a safe address; not read)
                     }
                     u32x4 tv[4];
@@ -590,7 +636,7 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
                     for (int i = 0; i < 4; ++i) {
                         if (!ok[i]) continue;
                         const uint32_t d = row[ks[i]];
-                        const uint32_t off = (uint32_t)(16 * (c0 + ks[i]) - kPadPos + 1) - left;
+                        const uint32_t off = 16u * (c0 + (uint32_t)ks[i] - kPadDw) + 1u - left;
                         const bool direct = src[i] != (gu8 *)P.kern;
                         for (uint32_t e = d & (d >> 1) & kLo; e; e &= e - 1u) {
                             const uint32_t f = (uint32_t)__builtin_ctz(e) >> 1;
@@ -600,7 +646,7 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
                             if (!has_ovf) {
                                 c = kEsc;
                             } else if (!direct || c == 255u) {
-                                c = ovf_lookup(U, trk, off + f + left);
+                                c = lookup(off + f + left);
                             }
                             if (ne < (uint32_t)kK3LEsc) ecache[ne] = (uint8_t)(c < 255u ? c : 255u);
                             ++ne;
@@ -613,7 +659,7 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
             if (staged) {
                 moments(nzm, j0);
             } else {
-                for (int64_t c0 = j0; c0 <= j1; c0 += kK3LRow) moments(stage(c0, j1, n0, n1), c0);
+                for (uint32_t c0 = j0; c0 <= j1; c0 += kK3LRow) moments(stage(c0, j1, j0, f0, j1, f1), c0);
             }
         } else if (live) {
             walk(false, [&](uint32_t pos, uint32_t c) {
@@ -628,36 +674,43 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
         double sum2 = 0.0, sum4 = 0.0;
         const bool heavy = live && nh > (uint32_t)P.heavy;
         if (live && !heavy) {
-            // per nonzero dword, all 16 fields at once: an empty field's
+            // per nonzero dword, all 16 fields: an empty field's
             // terms are +0.0, which leaves the (non-negative) sums unchanged
             // exactly, so the adds stay the hits' adds in position order
             // while the terms' FP64 work is independent across fields (a
             // loop over hits ran one dependent chain per hit)
             uint32_t ne = 0;
-            auto terms = [&](uint32_t m, int64_t c0) {
+            auto terms = [&](uint32_t m, uint32_t c0) {
                 while (m) {
                     const int k = __builtin_ctz(m);
                     m &= m - 1u;
                     const uint32_t d = row[k];
-                    const uint32_t off = (uint32_t)(16 * (c0 + k) - kPadPos + 1) - left;  // field 0's offset
-                    double t2[16], t4[16];
+                    const uint32_t off = 16u * (c0 + (uint32_t)k - kPadDw) + 1u - left;  // field 0's offset
+                    // (eight fields' terms at a time: sixteen held 64 registers,
+                    // the kernel's largest demand, for the path A/B runs alone take;
+                    // rolled: unrolled, the halves' terms were formed together again)
+#pragma nounroll
+                    for (int f0h = 0; f0h < 16; f0h += 8) {
+                        double t2[8], t4[8];
 #pragma unroll
-                    for (int f = 0; f < 16; ++f) {
-                        uint32_t c = (d >> (2 * f)) & 3u;
-                        if (c == kEsc) {
-                            c = ne < (uint32_t)kK3LEsc && ecache[ne] != 255u ? ecache[ne]
-                                                                             : ovf_lookup(U, trk, off + (uint32_t)f + left);
-                            ++ne;
+                        for (int fq = 0; fq < 8; ++fq) {
+                            const int f = f0h + fq;
+                            uint32_t c = (d >> (2 * f)) & 3u;
+                            if (c == kEsc) {
+                                c = ne < (uint32_t)kK3LEsc && ecache[ne] != 255u ? ecache[ne]
+                                                                                 : lookup(off + (uint32_t)f + left);
+                                ++ne;
+                            }
+                            const double dd = (double)(uint16_t)(off + (uint32_t)f) - x_bar;
+                            const double d2 = dd * dd;
+                            t2[fq] = c != 0u ? (double)c * d2 : 0.0;
+                            t4[fq] = c != 0u ? (double)c * (d2 * d2) : 0.0;
                         }
-                        const double dd = (double)(uint16_t)(off + (uint32_t)f) - x_bar;
-                        const double d2 = dd * dd;
-                        t2[f] = c != 0u ? (double)c * d2 : 0.0;
-                        t4[f] = c != 0u ? (double)c * (d2 * d2) : 0.0;
-                    }
 #pragma unroll
-                    for (int f = 0; f < 16; ++f) {
-                        sum2 = sum2 + t2[f];
-                        sum4 = sum4 + t4[f];
+                        for (int fq = 0; fq < 8; ++fq) {
+                            sum2 = sum2 + t2[fq];
+                            sum4 = sum4 + t4[fq];
+                        }
                     }
                 }
             };
@@ -665,9 +718,9 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
             // work), their terms formed independently, then added in order --
             // a dword holds ~5 hits, so this forms ~8 terms where the dword
             // form forms 16
-            auto hits4 = [&](uint32_t m, int64_t c0) {
+            auto hits4 = [&](uint32_t m, uint32_t c0) {
                 uint32_t d = 0;
-                int64_t j = 0;
+                uint32_t j = 0;
                 for (;;) {
                     uint32_t cv[4], ov[4];
 #pragma unroll
@@ -676,7 +729,7 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
                             const int k = __builtin_ctz(m);
                             m &= m - 1u;
                             d = row[k];
-                            j = c0 + k;
+                            j = c0 + (uint32_t)k;
                         }
                         cv[i] = 0u;
                         ov[i] = 0u;
@@ -684,7 +737,7 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
                             const int b = __builtin_ctz(d) & ~1;
                             cv[i] = (d >> b) & 3u;
                             d &= ~(3u << b);
-                            ov[i] = (uint32_t)(16 * j + b / 2 - kPadPos + 1) - left;  // pos - left
+                            ov[i] = 16u * (j - kPadDw) + (uint32_t)(b / 2) + 1u - left;  // pos - left
                         }
                     }
                     if (cv[0] == 0u) break;
@@ -692,7 +745,7 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
                     for (int i = 0; i < 4; ++i) {
                         if (cv[i] == kEsc) {
                             cv[i] = ne < (uint32_t)kK3LEsc && ecache[ne] != 255u ? ecache[ne]
-                                                                                 : ovf_lookup(U, trk, ov[i] + left);
+                                                                                 : lookup(ov[i] + left);
                             ++ne;
                         }
                     }
@@ -715,12 +768,12 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
                 if (staged) {
                     hits4(nzm, j0);
                 } else {
-                    for (int64_t c0 = j0; c0 <= j1; c0 += kK3LRow) hits4(stage(c0, j1, n0, n1), c0);
+                    for (uint32_t c0 = j0; c0 <= j1; c0 += kK3LRow) hits4(stage(c0, j1, j0, f0, j1, f1), c0);
                 }
             } else if (staged) {
                 terms(nzm, j0);
             } else {
-                for (int64_t c0 = j0; c0 <= j1; c0 += kK3LRow) terms(stage(c0, j1, n0, n1), c0);
+                for (uint32_t c0 = j0; c0 <= j1; c0 += kK3LRow) terms(stage(c0, j1, j0, f0, j1, f1), c0);
             }
         }
         // Regions with many hits would hold the whole wave in their lane's
@@ -785,7 +838,7 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
         if (P.cut == 3 && count == 12345u) P.out_counts[0] = (uint32_t)kurt;  // (+ both walks; keep them live)
         if (P.cut == 3) continue;
         double best = kval;
-        int64_t best_x = kpos;
+        uint32_t best_x = kpos;
         if (live && kn && P.qmode) {
             // score(kpos): the hit at kpos - bw + t adds kernel[2bw - t] *
             // countSum, in ascending t (positions outside the contig read 0)
@@ -797,22 +850,24 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
             // empty field's is +0.0, exact on the non-negative sum) and
             // their adds in position order; a dword's escaped counts come
             // from one 16-byte escape-tile load
-            const int64_t q0 = a0 >> 4, q1 = a1 >> 4;
-            for (int64_t c0 = q0; c0 <= q1; c0 += kK3LRow) {
-                uint32_t m = stage(c0, q1, a0, a1);
+            // (a0 >= kPadPos - bw - 1 > 0; the dword indices fit 32 bits)
+            const uint32_t q0 = (uint32_t)(a0 >> 4), q1 = (uint32_t)(a1 >> 4);
+            const uint32_t fa0 = (uint32_t)a0 & 15u, fa1 = (uint32_t)a1 & 15u;
+            for (uint32_t c0 = q0; c0 <= q1; c0 += kK3LRow) {
+                uint32_t m = stage(c0, q1, q0, fa0, q1, fa1);
                 while (m) {
                     const int k = __builtin_ctz(m);
                     m &= m - 1u;
                     const uint32_t d = row[k];
-                    const int64_t g0 = 16 * (c0 + k);  // field 0
+                    const uint32_t p1f = 16u * (c0 + (uint32_t)k - kPadDw);  // field 0's position - 1 (escapes lie in the contig)
+                    const int t0 = 16 * (int)(c0 + (uint32_t)k - q0) - (int)fa0;  // field 0's place in the window
                     u32x4 tv = {0u, 0u, 0u, 0u};
                     bool direct = false;
                     if ((d & (d >> 1) & kLo) != 0u && has_ovf) {
-                        const uint32_t p1f = (uint32_t)(g0 - kPadPos);  // field 0's position - 1 (escapes lie in the contig)
                         const uint32_t blk = p1f >> kOvfBlkShift;
                         const uint32_t ti = blk == b0 ? ti0 : blk == b0 + 1u ? ti1 : kNoTile;
                         if (ti != kNoTile) {
-                            tv = *(gu32x4 *)((gu8 *)U.ovf_tiles + (size_t)ti * kOvfBlk + (p1f & (kOvfBlk - 1u)));
+                            tv = *(gu32x4 *)(tiles + (size_t)ti * kOvfBlk + (p1f & (kOvfBlk - 1u)));
                             direct = true;
                         }
                     }
@@ -820,14 +875,13 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
 #pragma unroll
                     for (int fi = 0; fi < 16; ++fi) {
                         uint32_t c = (d >> (2 * fi)) & 3u;
-                        const int64_t g = g0 + fi;
                         if (c == kEsc) {
                             const uint32_t q = (uint32_t)fi >> 2;
                             const uint32_t w = q == 0 ? tv.x : q == 1 ? tv.y : q == 2 ? tv.z : tv.w;
                             const uint32_t v = (w >> (8 * (fi & 3))) & 255u;
-                            c = !has_ovf ? kEsc : (direct && v != 255u) ? v : ovf_lookup(U, trk, (uint32_t)(g - kPadPos + 1));
+                            c = !has_ovf ? kEsc : (direct && v != 255u) ? v : lookup(p1f + (uint32_t)fi + 1u);
                         }
-                        t[fi] = c != 0u ? ktab[2 * bw - (int)(g - a0)] * (double)c : 0.0;
+                        t[fi] = c != 0u ? ktab[2 * bw - (t0 + fi)] * (double)c : 0.0;
                     }
 #pragma unroll
                     for (int fi = 0; fi < 16; ++fi) f = f + t[fi];
@@ -845,6 +899,9 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
             tied &= tied - 1;
             const uint32_t tl = rl_u(left, l), tr = rl_u(right, l), tu = rl_u(u, l);
             const UnitDesc Ut = P.units[tu];
+            uint64_t wm[NWT];  // (the window masks: this path alone uses them)
+#pragma unroll
+            for (int d = -NH; d <= NH; ++d) wm[d + NH] = win_mask(d, bw);
             double tb = 0.0;
             int64_t tx = -1;
             for (int64_t x0 = tl; x0 <= (int64_t)tr; x0 += 64) {
@@ -871,7 +928,7 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
             }
             if (lane == l) {
                 best = tb;
-                best_x = tx;
+                best_x = (uint32_t)tx;
             }
         }
         if (P.cut == 5) continue;  // (+ the tied regions' KDE)
@@ -885,7 +942,7 @@ __global__ void __launch_bounds__(kK3LThreads) stats1L_kernel(StatParams P) {
             P.out_counts[ri] = count;  // exptSums[0]
             uint64_t *r = rstage + (uint64_t)lane * kK3LRecWords;
             r[0] = (uint64_t)u | ((uint64_t)left << 32);
-            r[1] = (uint64_t)right | ((uint64_t)(uint32_t)best_x << 32);
+            r[1] = (uint64_t)right | ((uint64_t)best_x << 32);
             r[2] = (uint64_t)count | ((uint64_t)nonctl << 32);
             r[3] = (uint64_t)(uint32_t)(acc ? 1 : 0) | ((uint64_t)UP_CLOSE_RULE << 32);
             r[4] = (uint64_t)__double_as_longlong(best);
