@@ -665,6 +665,68 @@ int up_dfl_segments(up_dfl *h, const void *src, const uint64_t *seg_off /* n_seg
 int up_dfl_timings(up_dfl *h, double *v, int n);
 int up_dfl_code_lengths(const uint32_t *freq, uint32_t n, uint32_t max_len, uint8_t *len);
 
+/* ---- bunzip: a bzip2 decoder, parallel over blocks --------------------------
+ * A .bz2 file is a chain of independent blocks.  The device path scans every
+ * bit offset for the two 48-bit magics, decodes every candidate block's
+ * entropy stage at once, links the candidates into the exact chain on the
+ * host (a candidate that no block ends at is a false positive and is dropped;
+ * a chain that breaks is a corrupt file), then runs the inverse BWT, the
+ * run-length stage and the CRCs per block.  Concatenated streams decode to
+ * the concatenation; anything else after a stream's end is an error.
+ *
+ * up_bz_decode: src is a whole file image in host memory; *out points at
+ * pinned host memory of the handle, valid until its next call.  Corrupt data
+ * is UP_E_ARG with info->reason (a UP_BZ_* code) and info->fail_bit set, and
+ * *n_out = 0: never a partial result.
+ *
+ * up_bz_scan: stage 1 alone.  Every bit offset at which a block magic
+ * (kind 0) or an end-of-stream magic (kind 1) stands, ascending; *n_cand is
+ * the full count, also when cap is smaller.
+ *
+ * up_bz_decode_host: the same block decoder (csrc/bz_block.h) on the host,
+ * serial along the chain; needs no device.  Writes at most cap bytes to dst;
+ * *n_out is the full decoded size.  A cap that is too small is UP_E_ARG with
+ * reason UP_BZ_NOSPACE and *n_out set, so a second call can succeed. */
+#define UP_BZ_OK 0
+#define UP_BZ_NOT_BZIP2 1   /* no "BZh" where a stream must start */
+#define UP_BZ_BAD_LEVEL 2   /* level byte outside '1'..'9' */
+#define UP_BZ_TRUNCATED 3   /* the data ends inside a stream */
+#define UP_BZ_BAD_MAGIC 4   /* neither a block nor an end magic where one must stand */
+#define UP_BZ_RANDOMISED 5  /* the pre-0.9.5 "randomised" bit is set */
+#define UP_BZ_ORIGPTR 6     /* origPtr not below the block's length */
+#define UP_BZ_SYMMAP 7      /* no symbol in use */
+#define UP_BZ_NGROUPS 8     /* coding tables outside 2..6 */
+#define UP_BZ_NSELECTORS 9  /* no selector */
+#define UP_BZ_SELECTOR 10   /* selector index >= nGroups, or selectors used up */
+#define UP_BZ_CODELEN 11    /* code length outside 1..20 */
+#define UP_BZ_BAD_CODE 12   /* bit pattern that no symbol owns */
+#define UP_BZ_OVERFLOW 13   /* more symbols than the block capacity */
+#define UP_BZ_BLOCK_CRC 14
+#define UP_BZ_STREAM_CRC 15
+#define UP_BZ_TRAILING 16   /* bytes after the last stream */
+#define UP_BZ_NOSPACE 17    /* up_bz_decode_host: dst too small (not a data error) */
+typedef struct up_bz_info {
+    uint32_t streams;  /* complete streams */
+    uint32_t blocks;   /* blocks on the chain */
+    uint32_t dropped;  /* scan candidates that were not on the chain */
+    int32_t reason;    /* UP_BZ_* */
+    uint64_t fail_bit; /* bit offset of the stream, block or field that failed */
+} up_bz_info_t;
+typedef struct up_bz up_bz;
+int up_bz_open(int device, up_bz **h);
+void up_bz_close(up_bz *h);
+int up_bz_decode(up_bz *h, const void *src, uint64_t n, const void **out, uint64_t *n_out,
+                 up_bz_info_t *info);
+int up_bz_scan(up_bz *h, const void *src, uint64_t n, uint64_t *bit_off, uint8_t *kind, uint64_t cap,
+               uint64_t *n_cand);
+/* totals since open, device ms: [0] scan, [1] entropy stage, [2] rank (successor vector),
+ * [3] inverse-BWT walks, [4] run-length stage and CRC; then [5] input bytes, [6] output
+ * bytes, [7] calls */
+int up_bz_timings(up_bz *h, double *v, int n);
+int up_bz_decode_host(const void *src, uint64_t n, void *dst, uint64_t cap, uint64_t *n_out,
+                      up_bz_info_t *info);
+const char *up_bz_reason(int reason);
+
 #ifdef __cplusplus
 }
 #endif

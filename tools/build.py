@@ -47,10 +47,10 @@ def _run(cmd, cwd=ROOT):
 
 
 def compile_lib(out, extra=(), jobs=None):
-    """libunipeak_hip.so from twelve translation units compiled in parallel:
+    """libunipeak_hip.so from thirteen translation units compiled in parallel:
     api.hip (C-ABI, non-templated kernels), tir.hip (tags_in_regions),
-    countmap.hip (convert_align), deflate.hip (the DEFLATE encoder) and
-    nh_tu.hip once per window width
+    countmap.hip (convert_align), deflate.hip (the DEFLATE encoder),
+    bzip2.hip (the bzip2 decoder) and nh_tu.hip once per window width
     NH = 1..8 (the templated K1/K3/K4 kernels)."""
     from concurrent.futures import ThreadPoolExecutor
     csrc = os.path.join(ROOT, "unipeak_amd", "csrc")
@@ -62,7 +62,8 @@ def compile_lib(out, extra=(), jobs=None):
     units = [("api", os.path.join(csrc, "api.hip"), []),
              ("tir", os.path.join(csrc, "tir.hip"), []),
              ("countmap", os.path.join(csrc, "countmap.hip"), []),
-             ("deflate", os.path.join(csrc, "deflate.hip"), [])] + [
+             ("deflate", os.path.join(csrc, "deflate.hip"), []),
+             ("bzip2", os.path.join(csrc, "bzip2.hip"), [])] + [
         (f"nh{k}", os.path.join(csrc, "nh_tu.hip"), [f"-DUPK_NH_TU={k}"]) for k in range(1, 9)]
     stamp = os.path.join(objdir, "flags.txt")  # objects built with other flags are stale
     same = os.path.exists(stamp) and open(stamp).read() == " ".join(flags)

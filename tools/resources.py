@@ -16,9 +16,10 @@ flt = args[0] if args else ""
 base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c",
         "-ffp-contract=off", "-I", f"{ROOT}/include", "-o", "/dev/null",
         "-Rpass-analysis=kernel-resource-usage"] + extra
-# api.hip (non-templated kernels), deflate.hip and the per-NH units (templated kernels)
+# api.hip (non-templated kernels), deflate.hip, bzip2.hip and the per-NH units (templated kernels)
 nhs = [int(x) for x in __import__("os").environ.get("NH", "1,2").split(",")]
-cmds = [base + [f"{ROOT}/unipeak_amd/csrc/api.hip"], base + [f"{ROOT}/unipeak_amd/csrc/deflate.hip"]] + [
+cmds = [base + [f"{ROOT}/unipeak_amd/csrc/api.hip"], base + [f"{ROOT}/unipeak_amd/csrc/deflate.hip"],
+        base + [f"{ROOT}/unipeak_amd/csrc/bzip2.hip"]] + [
     base + [f"-DUPK_NH_TU={k}", f"{ROOT}/unipeak_amd/csrc/nh_tu.hip"] for k in nhs]
 out = "\n".join(subprocess.run(c, capture_output=True, text=True).stderr for c in cmds)
 rows, cur = [], None

@@ -80,6 +80,8 @@ EXPORTS = [
     "up_cm_open", "up_cm_close", "up_cm_add", "up_cm_collect", "up_cm_timings",
     "up_dfl_open", "up_dfl_close", "up_dfl_block", "up_dfl_bound", "up_dfl_stream", "up_dfl_segments",
     "up_dfl_timings", "up_dfl_code_lengths",
+    "up_bz_open", "up_bz_close", "up_bz_decode", "up_bz_scan", "up_bz_timings", "up_bz_decode_host",
+    "up_bz_reason",
 ]
 # (up_set_wide_q11_nd, up_format_g6 and up_g6_to_float are bound in load_library like the rest; they are not listed here because
 # tests/test_capi.py compares this list with the header's names as its pattern reads them,
@@ -195,6 +197,13 @@ def load_library(path=LIB_PATH):
         "up_dfl_segments": (c.c_int, [vp, vp, vp, c.c_uint32, c.POINTER(vp), vp]),
         "up_dfl_timings": (c.c_int, [vp, vp, c.c_int]),
         "up_dfl_code_lengths": (c.c_int, [vp, c.c_uint32, c.c_uint32, vp]),
+        "up_bz_open": (c.c_int, [c.c_int, c.POINTER(vp)]),
+        "up_bz_close": (None, [vp]),
+        "up_bz_decode": (c.c_int, [vp, vp, c.c_uint64, c.POINTER(vp), c.POINTER(c.c_uint64), vp]),
+        "up_bz_scan": (c.c_int, [vp, vp, c.c_uint64, vp, vp, c.c_uint64, c.POINTER(c.c_uint64)]),
+        "up_bz_timings": (c.c_int, [vp, vp, c.c_int]),
+        "up_bz_decode_host": (c.c_int, [vp, c.c_uint64, vp, c.c_uint64, c.POINTER(c.c_uint64), vp]),
+        "up_bz_reason": (c.c_char_p, [c.c_int]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("UNIPEAK_LIB") and not hasattr(L, name):
@@ -768,4 +777,100 @@ class Deflate:
         """[device ms of the kernels, input bytes, output bytes, calls] since open"""
         t = np.zeros(4, np.float64)
         _ck(self.L.up_dfl_timings(self.h, t.ctypes.data, 4))
+        return t
+
+
+# UP_BZ_* reasons (include/unipeak_hip.h)
+(BZ_OK, BZ_NOT_BZIP2, BZ_BAD_LEVEL, BZ_TRUNCATED, BZ_BAD_MAGIC, BZ_RANDOMISED, BZ_ORIGPTR, BZ_SYMMAP,
+ BZ_NGROUPS, BZ_NSELECTORS, BZ_SELECTOR, BZ_CODELEN, BZ_BAD_CODE, BZ_OVERFLOW, BZ_BLOCK_CRC, BZ_STREAM_CRC,
+ BZ_TRAILING, BZ_NOSPACE) = range(18)
+
+
+class BzInfo(ctypes.Structure):  # up_bz_info_t
+    _fields_ = [
+        ("streams", ctypes.c_uint32),
+        ("blocks", ctypes.c_uint32),
+        ("dropped", ctypes.c_uint32),
+        ("reason", ctypes.c_int32),
+        ("fail_bit", ctypes.c_uint64),
+    ]
+
+
+class BzError(ValueError):
+    """corrupt bzip2 data: .reason is a BZ_* code, .info the whole up_bz_info_t"""
+
+    def __init__(self, info):
+        self.info, self.reason = info, int(info.reason)
+        text = load_library().up_bz_reason(self.reason).decode()
+        super().__init__(f"{text} (reason {self.reason}, bit {int(info.fail_bit)})")
+
+
+def _bz_result(rc, info):
+    if rc == -1 and info.reason != BZ_OK:  # UP_E_ARG with a reason: the data, not the call
+        raise BzError(info)
+    _ck(rc)
+
+
+def bunzip_host(data):
+    """(decoded bytes, BzInfo) through the host twin (up_bz_decode_host); BzError on corrupt data"""
+    L = load_library()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    src = buf.ctypes.data if len(buf) else None
+    cap = max(4 * len(buf), 1 << 16)
+    for _ in range(2):
+        dst, n, info = np.zeros(cap, np.uint8), ctypes.c_uint64(0), BzInfo()
+        rc = L.up_bz_decode_host(src, len(buf), dst.ctypes.data, cap, ctypes.byref(n), ctypes.byref(info))
+        if rc == -1 and info.reason == BZ_NOSPACE:
+            cap = int(n.value)  # the full size: the second call fits
+            continue
+        _bz_result(rc, info)
+        return dst[:n.value].tobytes(), info
+    raise RuntimeError("up_bz_decode_host: size changed between calls")
+
+
+class Bunzip:
+    """One up_bz handle: the bzip2 decoder on the device."""
+
+    def __init__(self, device=0):
+        self.L = load_library()
+        self.h = ctypes.c_void_p()
+        _ck(self.L.up_bz_open(device, ctypes.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.L.up_bz_close(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def decode(self, data):
+        """(decoded bytes, BzInfo) of a whole .bz2 file image; BzError on corrupt data"""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        out, n, info = ctypes.c_void_p(), ctypes.c_uint64(0), BzInfo()
+        rc = self.L.up_bz_decode(self.h, buf.ctypes.data if len(buf) else None, len(buf), ctypes.byref(out),
+                                 ctypes.byref(n), ctypes.byref(info))
+        _bz_result(rc, info)
+        return (ctypes.string_at(out.value, n.value) if n.value else b""), info
+
+    def scan(self, data):
+        """(bit offsets, kinds) of every block magic (kind 0) and end magic (kind 1), ascending"""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        src = buf.ctypes.data if len(buf) else None
+        n = ctypes.c_uint64(0)
+        _ck(self.L.up_bz_scan(self.h, src, len(buf), None, None, 0, ctypes.byref(n)))
+        bits, kinds = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint8)
+        if n.value:
+            _ck(self.L.up_bz_scan(self.h, src, len(buf), bits.ctypes.data, kinds.ctypes.data, n.value,
+                                  ctypes.byref(n)))
+        return bits, kinds
+
+    def timings(self):
+        """device ms of [scan, entropy, rank, walks, run-length + CRC], then input bytes, output
+        bytes and calls, since open"""
+        t = np.zeros(8, np.float64)
+        _ck(self.L.up_bz_timings(self.h, t.ctypes.data, 8))
         return t

@@ -1,6 +1,8 @@
 // unipeak_amd/host/gzio.cpp -- see gzio.hpp.  gzip streams are wrapped as
 // stdio FILEs (fopencookie over zlib's gzFile), so every reader and writer of
-// the CLIs keeps its FILE* code path.
+// the CLIs keeps its FILE* code path.  A ".bz2" input is decoded whole
+// (up_bz_decode_host, or up_bz_decode on the device with UNIPEAK_BZ_DEVICE=1) and read
+// from memory.
 #include "gzio.hpp"
 
 #include <sys/stat.h>
@@ -9,6 +11,7 @@
 #include <cerrno>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 
 #include "../../include/unipeak_hip.h"
 #include "cli.hpp"
@@ -25,9 +28,8 @@ static bool ends_with(const std::string &s, const char *suf) {
 bool is_gz(const std::string &fname) { return ends_with(fname, ".gz"); }
 bool is_bz2(const std::string &fname) { return ends_with(fname, ".bz2"); }
 
-[[noreturn]] static void no_bz2(const std::string &fname, const char *what) {
-    fatal(std::string("could not ") + what + " " + fname +
-          ": bzip2 (.bz2) streams are not supported by this build (libbz2 headers absent)");
+[[noreturn]] static void no_bz2_output(const std::string &fname) {
+    fatal("could not write " + fname + ": bzip2 (.bz2) output is not supported (input is read, output is not written)");
 }
 
 [[noreturn]] static void gz_fail(gzFile g, const std::string &what) {
@@ -153,8 +155,101 @@ size_t gz_isize_hint(const std::string &fname) {
 }
 }  // namespace
 
+namespace {
+// a decoded ".bz2" file behind a FILE*
+struct MemCookie {
+    std::string data;
+    size_t at = 0;
+};
+
+ssize_t mem_read(void *c, char *buf, size_t n) {
+    MemCookie *k = (MemCookie *)c;
+    const size_t take = std::min(n, k->data.size() - k->at);
+    std::memcpy(buf, k->data.data() + k->at, take);
+    k->at += take;
+    return (ssize_t)take;
+}
+
+int mem_close(void *c) {
+    delete (MemCookie *)c;
+    return 0;
+}
+
+bool read_whole(const std::string &fname, std::string &out) {
+    FILE *f = std::fopen(fname.c_str(), "rb");
+    if (!f) return false;
+    out.clear();
+    struct stat sb;
+    if (fstat(fileno(f), &sb) == 0 && sb.st_size > 0) out.reserve((size_t)sb.st_size);
+    char buf[1 << 16];
+    size_t k;
+    while ((k = std::fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, k);
+    std::fclose(f);
+    return true;
+}
+
+[[noreturn]] void bz_fail(const std::string &fname, const up_bz_info_t &info) {
+    fatal("could not read " + fname + ": " + up_bz_reason(info.reason) + " (bit " +
+          std::to_string((unsigned long long)info.fail_bit) + ")");
+}
+}  // namespace
+
+bool bunzip_file(const std::string &fname, std::string &out) {
+    std::string z;
+    if (!read_whole(fname, z)) return false;
+    // the host twin unless UNIPEAK_BZ_DEVICE=1 asks for the device: on the samples measured so far
+    // (9 and 24 blocks) the device path is the slower one
+    const char *e = std::getenv("UNIPEAK_BZ_DEVICE");
+    const bool device = e && *e && std::atoi(e) != 0;
+    up_bz_info_t info{};
+    double ms = 0;
+    out.clear();
+    if (device) {
+        up_bz *h = nullptr;
+        int rc = up_bz_open(cli_physical_device(0), &h);
+        if (rc != UP_OK) fatal("could not read " + fname + ": bzip2 decoder: " + up_strerror(rc));
+        const void *p = nullptr;
+        uint64_t n = 0;
+        rc = up_bz_decode(h, z.data(), z.size(), &p, &n, &info);
+        if (rc == UP_OK) {
+            out.assign((const char *)p, (size_t)n);
+            double v[5] = {0, 0, 0, 0, 0};
+            up_bz_timings(h, v, 5);
+            ms = v[0] + v[1] + v[2] + v[3] + v[4];
+        }
+        up_bz_close(h);
+        if (rc != UP_OK && info.reason != UP_BZ_OK) bz_fail(fname, info);
+        if (rc != UP_OK) fatal("could not read " + fname + ": bzip2 decoder: " + up_strerror(rc));
+    } else {
+        out.resize(std::max<size_t>(z.size() * 8, 1u << 16));
+        for (int pass = 0;; ++pass) {
+            uint64_t n = 0;
+            const int rc = up_bz_decode_host(z.data(), z.size(), &out[0], out.size(), &n, &info);
+            if (rc != UP_OK && info.reason == UP_BZ_NOSPACE && pass == 0) {
+                out.resize((size_t)n);  // the full size: the second pass fits
+                continue;
+            }
+            if (rc != UP_OK) bz_fail(fname, info);
+            out.resize((size_t)n);
+            break;
+        }
+    }
+    if (env_on("UNIPEAK_TIMING"))
+        std::fprintf(stderr, "[timing] bz2 %s in %llu B out %llu B blocks %u device %.3f ms path %s\n", fname.c_str(),
+                     (unsigned long long)z.size(), (unsigned long long)out.size(), info.blocks, ms,
+                     device ? "device" : "host");
+    return true;
+}
+
 FILE *open_input(const std::string &fname) {
-    if (is_bz2(fname)) no_bz2(fname, "read");
+    if (is_bz2(fname)) {
+        std::unique_ptr<MemCookie> k(new MemCookie);
+        if (!bunzip_file(fname, k->data)) return nullptr;
+        cookie_io_functions_t io{mem_read, nullptr, nullptr, mem_close};
+        FILE *f = fopencookie(k.get(), "r", io);
+        if (f) (void)k.release();  // mem_close deletes it
+        return f;
+    }
     if (!is_gz(fname)) return std::fopen(fname.c_str(), "rb");
     gzFile g = gzopen(fname.c_str(), "rb");
     if (!g) return nullptr;
@@ -171,7 +266,7 @@ FILE *open_input(const std::string &fname) {
 }
 
 FILE *open_output(const std::string &fname) {
-    if (is_bz2(fname)) no_bz2(fname, "write");
+    if (is_bz2(fname)) no_bz2_output(fname);
     if (!is_gz(fname)) return std::fopen(fname.c_str(), "wb");
     const bool timing = env_on("UNIPEAK_TIMING");
     const char *dev = std::getenv("UNIPEAK_GZ_DEVICE");

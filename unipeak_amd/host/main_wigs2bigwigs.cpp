@@ -21,6 +21,7 @@
 #include <zlib.h>
 
 #include "bbi.hpp"
+#include "gzio.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -213,10 +214,16 @@ std::string strip_re(const std::string &s, const std::string &suffix) {
 }
 
 bool read_lines(const std::string &path, std::vector<std::string> &out) {
-    // the Perl script pipes *.bz2 through bunzip2; libbz2 is not in this image
-    if (path.size() > 4 && path.compare(path.size() - 4, 4, ".bz2") == 0)
-        die("error: " + path + ": bzip2 (.bz2) input is not supported by this build; "
-            "decompress it first (bunzip2)\n");
+    // the Perl script pipes *.bz2 through bunzip2; here the project's decoder (gzio.hpp)
+    if (path.size() > 4 && path.compare(path.size() - 4, 4, ".bz2") == 0) {
+        std::string cur;
+        if (!unipeak::bunzip_file(path, cur)) return false;  // a corrupt stream is fatal in there
+        size_t b = 0;
+        for (size_t i = 0; i < cur.size(); ++i)
+            if (cur[i] == '\n') { out.push_back(cur.substr(b, i - b + 1)); b = i + 1; }
+        if (b < cur.size()) out.push_back(cur.substr(b));
+        return true;
+    }
     if (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) {
         gzFile g = gzopen(path.c_str(), "rb");
         if (!g) return false;

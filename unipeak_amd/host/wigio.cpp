@@ -233,10 +233,9 @@ std::shared_ptr<const LexedFile> LexedFile::open(const std::string &fname) {
     static std::unordered_map<std::string, std::weak_ptr<const LexedFile>> cache;
     std::lock_guard<std::mutex> lock(mu);
     if (auto sp = cache[fname].lock()) return sp;
-    if (is_bz2(fname)) return nullptr;  // LineReader refuses it (gzio.cpp)
-    if (is_gz(fname)) {
+    if (is_gz(fname) || is_bz2(fname)) {
         std::shared_ptr<LexedFile> f(new LexedFile());
-        if (!inflate_file(fname, f->inflated_)) return nullptr;
+        if (!(is_gz(fname) ? inflate_file(fname, f->inflated_) : bunzip_file(fname, f->inflated_))) return nullptr;
         f->size_ = f->inflated_.size();
         f->base_ = f->inflated_.data();
         f->lex_bytes();
@@ -268,7 +267,7 @@ LineReader::LineReader(const std::string &fname, bool lexed) {
         const char *nl = std::getenv("UNIPEAK_NO_LEX");  // tests: the plain getline reader
         if (lexed && !(nl && *nl && *nl != '0')) lexed_ = LexedFile::open(fname);
         if (!lexed_) {
-            fp_ = open_input(fname);  // ".gz" through zlib, ".bz2" refused (gzio.hpp)
+            fp_ = open_input(fname);  // ".gz" through zlib, ".bz2" through the bzip2 decoder (gzio.hpp)
             if (!fp_) {
                 std::cerr << "error: could not read " << fname << std::endl << std::endl;
                 exit_now(1);

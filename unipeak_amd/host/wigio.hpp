@@ -80,7 +80,7 @@ class LexedFile {
     void lex_bytes();
     const char *base_ = nullptr;
     uint64_t size_ = 0, lines_ = 0;
-    std::string inflated_;  // a ".gz" file's decompressed bytes (base_ points here)
+    std::string inflated_;  // a ".gz" / ".bz2" file's decompressed bytes (base_ points here)
     std::vector<Chunk> chunks_;
 };
 
